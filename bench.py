@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the spherical-BA hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Metric (BASELINE.json): residual+Jacobian evaluations per second.  Workload at N = 1: BASELINE config
@@ -10,7 +10,13 @@ correspondences with per-match depths (64 algorithmic bytes per evaluation: 2 x 
 components + 2 f64 depths), f64 arithmetic.  At N > 1: one GPU's shard of BASELINE config C4 ("100M
 correspondences sharded 8xMI355X") = 12.5M of the same correspondences per GPU, one RCCL all-reduce of the
 24-double pack per step (the collective north_star names; `--transport peer` selects the direct xGMI exchange).
-At N = 1 the line also carries `c1`: BASELINE config C1 (the reference's real workload: 2 048 matches, initial guess + d-only +
+
+A plain run sets up, pre-conditions and warms up, times the K steps, writes the last timed step's outputs if
+`--dump-outputs DIR` is given (the 24-double pack as DIR/pack.npy; `--workload c5`: every pair's pack as DIR/packs.npy),
+and prints the headline line.  Every secondary figure described below (`cold`, `roofline`, `lm`, `cpu_baseline`,
+`scaling_reference`, `stages`, `c1`, `c2`, `c5`; for `--workload c5` its roofline, LM, stage, pipeline and remap
+figures) is taken only with `--full`; the `--no-...` options select among them there.
+With `--full`, at N = 1 the line also carries `c1`: BASELINE config C1 (the reference's real workload: 2 048 matches, initial guess + d-only +
 rot-only + tran-only end to end, GPU beside the oracle's pipeline on the host cores; `--no-c1-leg`, which also drops `c2`:
 BASELINE config C2, 1M rotation-only), `c5`: BASELINE config C5 (256 pairs x 50k: batched step, per-pair LM, 512-frame remap) from a
 child run of `--workload c5` after the timed region (`--no-c5-leg` skips it), and `stages`: the 8-point initial guess and the
@@ -93,7 +99,22 @@ def parse():
                     help="skip the W + K steps taken BEFORE the pre-conditioning (`cold` in the line)")
     ap.add_argument("--no-scaling-reference", action="store_true",
                     help="N = 1: skip the K steps at 12.5M correspondences (`scaling_reference`: the per-GPU size of N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take every secondary figure (cold leg, kernel-only roofline timings, LM rate, stream probe, "
+                         "CPU baseline, scaling reference, stages, configs C1 / C2 / C5); off by default: a plain run "
+                         "times the K steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step, one DIR/<name>.npy each."""
+    import numpy as np
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def usable_cores() -> int:
@@ -208,12 +229,13 @@ def run_c5(a):
         t_up = time.perf_counter()
         b.upload(x1, x2, off, d12)
         upload_s = time.perf_counter() - t_up
-        t_up = time.perf_counter()
-        b.upload(x1, x2, off, d12)                  # same pairs again: every allocation is reused, only the data moves
-        reupload_s = time.perf_counter() - t_up
-        t_up = time.perf_counter()
-        b.set_depths(d12)
-        set_depths_s = time.perf_counter() - t_up
+        if a.full:
+            t_up = time.perf_counter()
+            b.upload(x1, x2, off, d12)                  # same pairs again: every allocation is reused, only the data moves
+            reupload_s = time.perf_counter() - t_up
+            t_up = time.perf_counter()
+            b.set_depths(d12)
+            set_depths_s = time.perf_counter() - t_up
         barrier()
         precond = {"sweeps": 0, "ms": 0.0}
         if a.precondition_ms > 0:
@@ -234,138 +256,142 @@ def run_c5(a):
             t = torch.tensor([elapsed], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        # the last timed step's packs, one row per pair (each rank holds its own pairs)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"packs" if world == 1 else f"packs_rank{rank}": packs})
         # the dominant kernel of the step just timed: batch_step_kernel (the whole step in one launch) with one block per
         # pair, batch_sweep_kernel otherwise
         fused = b.step_is_fused
-        per_launch = b.step_launch_times(api.MODE_RT, rot0, tran0, repeat=max(a.steps, 20), **kw)
-        sweep_alone = b.sweep_launch_times(api.MODE_RT, rot0, tran0, repeat=max(a.steps, 20), **kw) if fused else per_launch
-        # per-pair LM: all pairs solved in lock-step off the batched launches
-        opt = api.default_lm_options(tran_param=api.TRAN_SPHERE)
-        b.solve(api.MODE_RT, rot0, tran0, options=opt, **kw)
-        lm_times = []
-        for _ in range(5):          # median: the Python wrapper builds 256 summary objects per call, and one call in a few pays a GC pass
-            t_lm = time.perf_counter()
-            rot, tran, sums, status = b.solve(api.MODE_RT, rot0, tran0, options=opt, **kw)
-            lm_times.append(time.perf_counter() - t_lm)
-        lm_s = float(np.median(lm_times))
         bpp = b.blocks_per_pair
-        # the d-only stage of every pair (the first stage of solve_problem, reference .cpp:196-197): one launch, one solver per
-        # pair on the device (SBA_BATCH_DEVICE_DEPTH=0: host solvers in lock-step, one launch per pass)
-        depth = None
-        try:
-            d0 = np.full((B * n, 2), 5.0)
-            b.upload(x1, x2, off, d0)
-            b.solve_depths(rot0, tran0, want_depths=False)               # first call: scratch allocations
-            b.upload(x1, x2, off, d0)
-            t_d = time.perf_counter()
-            _, dsums, dstatus = b.solve_depths(rot0, tran0, want_depths=False)     # the refined depths stay on the device
-            d_s = time.perf_counter() - t_d
-            passes = max(q.num_evaluations for q in dsums)
-            pair_passes = sum(q.num_evaluations for q in dsums)         # a pair leaves the lock-step when it has converged
-            one_launch = os.environ.get("SBA_BATCH_DEVICE_DEPTH", "1") != "0"
-            cap = os.environ.get("SBA_BATCH_DEPTH_FIRST_PASSES", "16")
-            depth = {"seconds": d_s,
-                     "driver": ((f"per-pair solvers on the device: first {cap} passes in one launch, the rest in launches with dynamic shares" if cap != "0"
-                                 else "per-pair solvers on the device, one launch to the end") if one_launch else "host lock-step, one launch per pass"),
-                     "passes_longest_pair": passes, "pair_passes": pair_passes,
-                     "iterations_min_max": [min(q.num_iterations for q in dsums), max(q.num_iterations for q in dsums)],
-                     "us_per_pass": d_s / max(passes, 1) * 1e6, "all_converged": bool((dstatus == 0).all() and all(q.termination.startswith("CONV") for q in dsums)),
-                     "algorithmic_bytes": pair_passes * n * 96,
-                     "frac": pair_passes * n * 96 / d_s / 1e9 / HBM_PEAK_GBPS,
-                     "ideal_balanced_s": pair_passes * n * 96 / (0.72 * HBM_PEAK_GBPS * 1e9),
-                     "what": "sba_batch_solve_depths: every pair's bounded d-only problem (own trust region, line search, convergence), "
-                             "start d = 5 (pairs need 9-36 iterations); ideal_balanced_s = the same pair-passes spread evenly over the "
-                             "device at the d-only kernel's own 0.72 of peak (one launch to the end is paced by the longest pair's passes "
-                             "on its one CU; the default hands the late passes to launches whose blocks are dealt to the pairs still iterating)"}
-        except Exception as e:      # noqa: BLE001 -- a secondary figure must never take the line down
-            depth = {"ok": False, "error": f"{type(e).__name__}: {e}"}
-        # the 8-point initial guess of every pair (reference .cpp:47-181): group moments of all pairs in one launch + trials
-        guess = None
-        try:
-            b.initial_guess(80, 0.25, 1, check=False)
-            t_g = time.perf_counter()
-            ge, gt, gnc, gst = b.initial_guess(80, 0.25, 1, check=False)       # moments, 80 trials, consensus: all on the device
-            g_dev = time.perf_counter() - t_g
-            t_g = time.perf_counter()
-            b.epipolar_moments()
-            g_mom = time.perf_counter() - t_g
-            os.environ["SBA_BATCH_DEVICE_GUESS"] = "0"
+        if a.full:
+            per_launch = b.step_launch_times(api.MODE_RT, rot0, tran0, repeat=max(a.steps, 20), **kw)
+            sweep_alone = b.sweep_launch_times(api.MODE_RT, rot0, tran0, repeat=max(a.steps, 20), **kw) if fused else per_launch
+            # per-pair LM: all pairs solved in lock-step off the batched launches
+            opt = api.default_lm_options(tran_param=api.TRAN_SPHERE)
+            b.solve(api.MODE_RT, rot0, tran0, options=opt, **kw)
+            lm_times = []
+            for _ in range(5):          # median: the Python wrapper builds 256 summary objects per call, and one call in a few pays a GC pass
+                t_lm = time.perf_counter()
+                rot, tran, sums, status = b.solve(api.MODE_RT, rot0, tran0, options=opt, **kw)
+                lm_times.append(time.perf_counter() - t_lm)
+            lm_s = float(np.median(lm_times))
+            # the d-only stage of every pair (the first stage of solve_problem, reference .cpp:196-197): one launch, one solver per
+            # pair on the device (SBA_BATCH_DEVICE_DEPTH=0: host solvers in lock-step, one launch per pass)
+            depth = None
             try:
-                t_g = time.perf_counter()
-                he, ht, hnc, hst = b.initial_guess(80, 0.25, 1, check=False)
-                g_1 = time.perf_counter() - t_g
-                api.set_host_threads(0)
-                t_g = time.perf_counter()
+                d0 = np.full((B * n, 2), 5.0)
+                b.upload(x1, x2, off, d0)
+                b.solve_depths(rot0, tran0, want_depths=False)               # first call: scratch allocations
+                b.upload(x1, x2, off, d0)
+                t_d = time.perf_counter()
+                _, dsums, dstatus = b.solve_depths(rot0, tran0, want_depths=False)     # the refined depths stay on the device
+                d_s = time.perf_counter() - t_d
+                passes = max(q.num_evaluations for q in dsums)
+                pair_passes = sum(q.num_evaluations for q in dsums)         # a pair leaves the lock-step when it has converged
+                one_launch = os.environ.get("SBA_BATCH_DEVICE_DEPTH", "1") != "0"
+                cap = os.environ.get("SBA_BATCH_DEPTH_FIRST_PASSES", "16")
+                depth = {"seconds": d_s,
+                         "driver": ((f"per-pair solvers on the device: first {cap} passes in one launch, the rest in launches with dynamic shares" if cap != "0"
+                                     else "per-pair solvers on the device, one launch to the end") if one_launch else "host lock-step, one launch per pass"),
+                         "passes_longest_pair": passes, "pair_passes": pair_passes,
+                         "iterations_min_max": [min(q.num_iterations for q in dsums), max(q.num_iterations for q in dsums)],
+                         "us_per_pass": d_s / max(passes, 1) * 1e6, "all_converged": bool((dstatus == 0).all() and all(q.termination.startswith("CONV") for q in dsums)),
+                         "algorithmic_bytes": pair_passes * n * 96,
+                         "frac": pair_passes * n * 96 / d_s / 1e9 / HBM_PEAK_GBPS,
+                         "ideal_balanced_s": pair_passes * n * 96 / (0.72 * HBM_PEAK_GBPS * 1e9),
+                         "what": "sba_batch_solve_depths: every pair's bounded d-only problem (own trust region, line search, convergence), "
+                                 "start d = 5 (pairs need 9-36 iterations); ideal_balanced_s = the same pair-passes spread evenly over the "
+                                 "device at the d-only kernel's own 0.72 of peak (one launch to the end is paced by the longest pair's passes "
+                                 "on its one CU; the default hands the late passes to launches whose blocks are dealt to the pairs still iterating)"}
+            except Exception as e:      # noqa: BLE001 -- a secondary figure must never take the line down
+                depth = {"ok": False, "error": f"{type(e).__name__}: {e}"}
+            # the 8-point initial guess of every pair (reference .cpp:47-181): group moments of all pairs in one launch + trials
+            guess = None
+            try:
                 b.initial_guess(80, 0.25, 1, check=False)
-                g_auto = time.perf_counter() - t_g
-            finally:
-                api.set_host_threads(1)
-                del os.environ["SBA_BATCH_DEVICE_GUESS"]
-            guess = {"seconds": g_dev, "pairs_per_s": B / g_dev, "seconds_moments_and_copy_alone": g_mom,
-                     "seconds_host_trials_1_thread": g_1, "seconds_host_trials_auto_threads": g_auto,
-                     "pairs_with_a_candidate": int((gst == 0).sum()), "moments_algorithmic_bytes": B * n * 48,
-                     "max_abs_difference_to_host_trials": float(max(np.abs(ge - he).max(), np.abs(gt - ht).max())),
-                     "what": "sba_batch_initial_guess: 64 x 45 group moments of every pair in one launch, then 80 trials + consensus "
-                             "pick per pair in a second (one block per pair); host-trial figures: SBA_BATCH_DEVICE_GUESS=0"}
-        except Exception as e:      # noqa: BLE001
-            guess = {"ok": False, "error": f"{type(e).__name__}: {e}"}
-        # the reference's whole per-pair pipeline for every pair (initial guess -> d-only -> rot-only -> tran-only), and the
-        # oracle's pipeline for a few of the same pairs on the host cores
-        pipeline = None
-        try:
-            d0 = np.full((B * n, 2), 6.0)
-            b.upload(x1, x2, off, d0)
-            b.solve_problem(seed=1, check=False)
-            times, inside = [], []
-            for _ in range(5):
-                b.set_depths(d0)
-                t_p = time.perf_counter()
-                res = b.solve_problem(seed=1, check=False)
-                times.append(time.perf_counter() - t_p)
-                inside.append(res["seconds_inside_the_library"])
-            p_s = float(np.median(inside))
-            counts = lambda g: (res["depth_stage"][g].num_iterations, res["depth_stage"][g].num_line_search_steps,   # noqa: E731
-                                res["rot_stage"][g].num_iterations, res["tran_stage"][g].num_iterations)
-            pipeline = {"seconds": p_s, "seconds_with_the_python_wrapper": float(np.median(times)), "pairs_per_s": B / p_s,
-                        "pairs_ok": int((res["status"] == 0).sum()),
-                        "iterations_min_median_max": {k: [int(np.min(v)), float(np.median(v)), int(np.max(v))] for k, v in
-                                                      ((st, [q.num_iterations for q in res[st]]) for st in ("depth_stage", "rot_stage", "tran_stage"))},
-                        "evaluations_sum_and_max": {k: [int(np.sum(v)), int(np.max(v))] for k, v in
-                                                    ((st, [q.num_evaluations for q in res[st]]) for st in ("depth_stage", "rot_stage", "tran_stage"))},
-                        "what": "sba_batch_solve_problem: 8-point consensus guess, d-only, rot-only, tran-only for all pairs "
-                                "(start d = 6); depths already resident; the C call alone, median of 5 (the Python wrapper then builds "
-                                "3 x 256 summary objects)"}
-            if rank == 0:       # three pairs, well under a second: also in the child run of the default line
-                from oracle import oracle_py as orc
-                sample = [0, B // 2, B - 1][:max(1, min(3, B))]
-                cores = max(1, min(orc.num_procs(), usable_cores()))
-                e_g, t_g2, _, _ = b.initial_guess(80, 0.25, 1, check=False)
+                t_g = time.perf_counter()
+                ge, gt, gnc, gst = b.initial_guess(80, 0.25, 1, check=False)       # moments, 80 trials, consensus: all on the device
+                g_dev = time.perf_counter() - t_g
+                t_g = time.perf_counter()
+                b.epipolar_moments()
+                g_mom = time.perf_counter() - t_g
+                os.environ["SBA_BATCH_DEVICE_GUESS"] = "0"
+                try:
+                    t_g = time.perf_counter()
+                    he, ht, hnc, hst = b.initial_guess(80, 0.25, 1, check=False)
+                    g_1 = time.perf_counter() - t_g
+                    api.set_host_threads(0)
+                    t_g = time.perf_counter()
+                    b.initial_guess(80, 0.25, 1, check=False)
+                    g_auto = time.perf_counter() - t_g
+                finally:
+                    api.set_host_threads(1)
+                    del os.environ["SBA_BATCH_DEVICE_GUESS"]
+                guess = {"seconds": g_dev, "pairs_per_s": B / g_dev, "seconds_moments_and_copy_alone": g_mom,
+                         "seconds_host_trials_1_thread": g_1, "seconds_host_trials_auto_threads": g_auto,
+                         "pairs_with_a_candidate": int((gst == 0).sum()), "moments_algorithmic_bytes": B * n * 48,
+                         "max_abs_difference_to_host_trials": float(max(np.abs(ge - he).max(), np.abs(gt - ht).max())),
+                         "what": "sba_batch_initial_guess: 64 x 45 group moments of every pair in one launch, then 80 trials + consensus "
+                                 "pick per pair in a second (one block per pair); host-trial figures: SBA_BATCH_DEVICE_GUESS=0"}
+            except Exception as e:      # noqa: BLE001
+                guess = {"ok": False, "error": f"{type(e).__name__}: {e}"}
+            # the reference's whole per-pair pipeline for every pair (initial guess -> d-only -> rot-only -> tran-only), and the
+            # oracle's pipeline for a few of the same pairs on the host cores
+            pipeline = None
+            try:
+                d0 = np.full((B * n, 2), 6.0)
+                b.upload(x1, x2, off, d0)
+                b.solve_problem(seed=1, check=False)
+                times, inside = [], []
+                for _ in range(5):
+                    b.set_depths(d0)
+                    t_p = time.perf_counter()
+                    res = b.solve_problem(seed=1, check=False)
+                    times.append(time.perf_counter() - t_p)
+                    inside.append(res["seconds_inside_the_library"])
+                p_s = float(np.median(inside))
+                counts = lambda g: (res["depth_stage"][g].num_iterations, res["depth_stage"][g].num_line_search_steps,   # noqa: E731
+                                    res["rot_stage"][g].num_iterations, res["tran_stage"][g].num_iterations)
+                pipeline = {"seconds": p_s, "seconds_with_the_python_wrapper": float(np.median(times)), "pairs_per_s": B / p_s,
+                            "pairs_ok": int((res["status"] == 0).sum()),
+                            "iterations_min_median_max": {k: [int(np.min(v)), float(np.median(v)), int(np.max(v))] for k, v in
+                                                          ((st, [q.num_iterations for q in res[st]]) for st in ("depth_stage", "rot_stage", "tran_stage"))},
+                            "evaluations_sum_and_max": {k: [int(np.sum(v)), int(np.max(v))] for k, v in
+                                                        ((st, [q.num_evaluations for q in res[st]]) for st in ("depth_stage", "rot_stage", "tran_stage"))},
+                            "what": "sba_batch_solve_problem: 8-point consensus guess, d-only, rot-only, tran-only for all pairs "
+                                    "(start d = 6); depths already resident; the C call alone, median of 5 (the Python wrapper then builds "
+                                    "3 x 256 summary objects)"}
+                if rank == 0:       # three pairs, well under a second: also in the child run of the default line
+                    from oracle import oracle_py as orc
+                    sample = [0, B // 2, B - 1][:max(1, min(3, B))]
+                    cores = max(1, min(orc.num_procs(), usable_cores()))
+                    e_g, t_g2, _, _ = b.initial_guess(80, 0.25, 1, check=False)
 
-                def cpu_pairs(threads):
-                    ts, ok, diff = [], True, 0.0
-                    for g in sample:
-                        c = cs[g]
-                        t_c = time.perf_counter()
-                        rot_s, tran_s = -e_g[g], t_g2[g]            # the oracle has no group-sampled guess of its own: stages only
-                        dd, sdd, _ = orc.depth_solve(c.x1, c.x2, rot_s, tran_s, d0[:n])
-                        r1, t1, s1, _ = orc.lm_solve(0, c.x1, c.x2, rot_s, tran_s, dd[0, 0], dd[1, 0], threads=threads)
-                        r2, t2, s2, _ = orc.lm_solve(1, c.x1, c.x2, r1, t1, dd[0, 0], dd[1, 0], threads=threads)
-                        ts.append(time.perf_counter() - t_c)
-                        ok = ok and (sdd.num_iterations, sdd.num_line_search_steps, s1.num_iterations, s2.num_iterations) == counts(g)
-                        diff = max(diff, float(np.abs(res["rot"][g] - r2).max()))
-                    return ts, ok, diff
-                runs = {th: cpu_pairs(th) for th in sorted({1, cores})}     # more threads than granted cores only add wake-ups
-                cores = min(runs, key=lambda k: np.mean(runs[k][0]))
-                cpu_t, agree, rot_diff = runs[cores]
-                per_pair = float(np.mean(cpu_t))
-                pipeline["cpu_oracle"] = {"seconds_per_pair": per_pair, "pairs_per_s": 1.0 / per_pair, "pairs_sampled": sample,
-                                          "cores": cores, "iteration_counts_equal": bool(agree), "max_abs_rot_diff": rot_diff,
-                                          "what": "oracle/sba_oracle.cpp: the three solve stages of the same pairs from the same "
-                                                  "start values (the 8-point guess is not part of this figure)"}
-        except Exception as e:      # noqa: BLE001
-            pipeline = {"ok": False, "error": f"{type(e).__name__}: {e}"}
+                    def cpu_pairs(threads):
+                        ts, ok, diff = [], True, 0.0
+                        for g in sample:
+                            c = cs[g]
+                            t_c = time.perf_counter()
+                            rot_s, tran_s = -e_g[g], t_g2[g]            # the oracle has no group-sampled guess of its own: stages only
+                            dd, sdd, _ = orc.depth_solve(c.x1, c.x2, rot_s, tran_s, d0[:n])
+                            r1, t1, s1, _ = orc.lm_solve(0, c.x1, c.x2, rot_s, tran_s, dd[0, 0], dd[1, 0], threads=threads)
+                            r2, t2, s2, _ = orc.lm_solve(1, c.x1, c.x2, r1, t1, dd[0, 0], dd[1, 0], threads=threads)
+                            ts.append(time.perf_counter() - t_c)
+                            ok = ok and (sdd.num_iterations, sdd.num_line_search_steps, s1.num_iterations, s2.num_iterations) == counts(g)
+                            diff = max(diff, float(np.abs(res["rot"][g] - r2).max()))
+                        return ts, ok, diff
+                    runs = {th: cpu_pairs(th) for th in sorted({1, cores})}     # more threads than granted cores only add wake-ups
+                    cores = min(runs, key=lambda k: np.mean(runs[k][0]))
+                    cpu_t, agree, rot_diff = runs[cores]
+                    per_pair = float(np.mean(cpu_t))
+                    pipeline["cpu_oracle"] = {"seconds_per_pair": per_pair, "pairs_per_s": 1.0 / per_pair, "pairs_sampled": sample,
+                                              "cores": cores, "iteration_counts_equal": bool(agree), "max_abs_rot_diff": rot_diff,
+                                              "what": "oracle/sba_oracle.cpp: the three solve stages of the same pairs from the same "
+                                                      "start values (the 8-point guess is not part of this figure)"}
+            except Exception as e:      # noqa: BLE001
+                pipeline = {"ok": False, "error": f"{type(e).__name__}: {e}"}
     remap = None
-    if rank == 0 and a.frames > 0:
+    if a.full and rank == 0 and a.frames > 0:
         # "equi2cube remap on GPU": device-resident frames, 3840x1920 -> S = 600 strip, 6 B per output pixel
         lib = cabi.load_library()
         F, H, W, S = a.frames, 1920, 3840, 600
@@ -388,9 +414,6 @@ def run_c5(a):
         del src, dst
     if rank == 0:
         total = B * n * world
-        sweep_ms = float(per_launch.mean())
-        kernel_name = ("batch_step_kernel" if fused else "batch_sweep_kernel") + "<2, 1, double, 0, true>"
-        achieved = B * n * 64 / (sweep_ms * 1e-3) / 1e9
         out = {
             "metric": "residual+Jacobian evals/sec", "value": total * a.steps / elapsed, "unit": "evals/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
@@ -404,6 +427,15 @@ def run_c5(a):
                                 "packs awaited by the host") if fused else
                                ("prepare kernel (per-pair sweep state) + batch_sweep_kernel + fold/convert/publish kernel, "
                                 "packs awaited by the host")},
+            "preconditioning": {**precond, "what": "un-timed launches of the same kernel before the warm-up steps"},
+            "step_split_ms": split,
+            "upload_s": upload_s, "upload_bytes": int(B * n * 64),
+        }
+    if rank == 0 and a.full:
+        sweep_ms = float(per_launch.mean())
+        kernel_name = ("batch_step_kernel" if fused else "batch_sweep_kernel") + "<2, 1, double, 0, true>"
+        achieved = B * n * 64 / (sweep_ms * 1e-3) / 1e9
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc_traffic_named(kernel_name.split("<")[0], B * n),
                          "kernel": kernel_name, "kernel_ms": sweep_ms,
@@ -415,16 +447,13 @@ def run_c5(a):
                          "sweep_kernel_alone": {"kernel": "batch_sweep_kernel<2, 1, double, 0, true>",
                                                 "kernel_ms": float(sweep_alone.mean()),
                                                 "frac": B * n * 64 / (float(sweep_alone.mean()) * 1e-3) / 1e9 / HBM_PEAK_GBPS}},
-            "preconditioning": {**precond, "what": "un-timed launches of the same kernel before the warm-up steps"},
-            "step_split_ms": split,
             "lm": {"pairs_per_s": B / lm_s, "seconds": lm_s, "seconds_inside_the_library": max(s_.seconds_total for s_ in sums),
                    "max_iterations": max(s_.num_iterations for s_ in sums),
                    "all_converged": bool((status == 0).all() and all(s_.termination.startswith("CONV") for s_ in sums)),
                    "max_rot_err_rad": float(max(np.abs(rot[g] - cs[g].rot_true).max() for g in range(B)))},
             "depth_stage": depth, "initial_guess": guess, "pipeline": pipeline,
-            "equi2cube": remap, "upload_s": upload_s, "reupload_s": reupload_s, "set_depths_s": set_depths_s,
-            "upload_bytes": int(B * n * 64),
-        }
+            "equi2cube": remap, "reupload_s": reupload_s, "set_depths_s": set_depths_s,
+        })
         if not a.no_cpu_baseline and world == 1:
             from oracle import oracle_py as orc
             cores = min(orc.num_procs(), usable_cores())
@@ -440,6 +469,7 @@ def run_c5(a):
             out["cpu_baseline"] = {"value": take * n * passes / el, "unit": "evals/s", "cores": cores, "kind": "port",
                                    "sample": f"{passes} passes over the first {take} pairs ({take * n} correspondences), faithful "
                                              f"dual-number loop with f64 accumulation, {cores} OpenMP threads"}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()
@@ -630,7 +660,7 @@ def c5_leg(steps: int, warmup: int):
     import subprocess
     try:
         r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "c5", "--steps", str(steps), "--warmup", str(warmup),
-                            "--no-cpu-baseline"], capture_output=True, text=True, timeout=240, cwd=str(ROOT))
+                            "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=240, cwd=str(ROOT))
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         if r.returncode != 0 or not lines:
             return {"ok": False, "error": (r.stderr or r.stdout)[-300:]}
@@ -796,9 +826,9 @@ def main():
     barrier()   # ranks generate and upload their shards at different speeds: enter the first exchange together
     # `cold`: the command line taken literally -- W warm-up + K timed steps straight after the upload, BEFORE any
     # pre-conditioning (what round 1's driver run measured: the K steps fall into the clock dip after the first ~1.5 ms
-    # of load).  Reported beside the quoted value, never instead of it.
+    # of load).  Reported beside the quoted value, never instead of it (--full only).
     cold = None
-    if not a.no_cold_leg:
+    if a.full and not a.no_cold_leg:
         if a.warmup > 0:
             p.eval_steps(mode, rot, tran, depth_mode=depth_mode, steps=a.warmup)
         barrier()
@@ -832,19 +862,23 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # the last timed step's pack (after the all-reduce at N > 1: the same on every rank)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"pack": pack})
 
-    # kernel-only timing (HIP events on the problem's stream, same K sweeps) for the roofline figure
-    _, step_ms, sweep_ms = p.eval_timed(mode, rot, tran, depth_mode=depth_mode, repeat=a.steps)
-    # ... and launch by launch (an event between every two launches: each figure includes one event boundary, so the
-    # mean of these sits 1-2 us above sweep_ms): the spread a mean hides
-    per_launch = p.eval_launch_times(mode, rot, tran, depth_mode=depth_mode, repeat=max(a.steps, 20))
-    # LM iterations per second of a real solve of this workload (secondary metric)
-    opt = api.default_lm_options(tran_param=api.TRAN_SPHERE if rt else api.TRAN_FREE)
-    p.solve(mode, c.rot_init, c.tran_init, depth_mode=depth_mode, options=opt)         # first call: one-time costs
-    # median of several solves: a single 3-iteration solve is ~0.4 ms and one scheduling hiccup doubles it
-    # (profiles/r03_lm_rate.log); every rank runs the same number of solves (each is a sequence of collectives at N > 1)
-    lm_runs = [p.solve(mode, c.rot_init, c.tran_init, depth_mode=depth_mode, options=opt) for _ in range(7)]
-    r_s, t_s, summ = sorted(lm_runs, key=lambda q: q[2].seconds_total)[len(lm_runs) // 2]
+    if a.full:
+        # kernel-only timing (HIP events on the problem's stream, same K sweeps) for the roofline figure
+        _, step_ms, sweep_ms = p.eval_timed(mode, rot, tran, depth_mode=depth_mode, repeat=a.steps)
+        # ... and launch by launch (an event between every two launches: each figure includes one event boundary, so the
+        # mean of these sits 1-2 us above sweep_ms): the spread a mean hides
+        per_launch = p.eval_launch_times(mode, rot, tran, depth_mode=depth_mode, repeat=max(a.steps, 20))
+        # LM iterations per second of a real solve of this workload (secondary metric)
+        opt = api.default_lm_options(tran_param=api.TRAN_SPHERE if rt else api.TRAN_FREE)
+        p.solve(mode, c.rot_init, c.tran_init, depth_mode=depth_mode, options=opt)         # first call: one-time costs
+        # median of several solves: a single 3-iteration solve is ~0.4 ms and one scheduling hiccup doubles it
+        # (profiles/r03_lm_rate.log); every rank runs the same number of solves (each is a sequence of collectives at N > 1)
+        lm_runs = [p.solve(mode, c.rot_init, c.tran_init, depth_mode=depth_mode, options=opt) for _ in range(7)]
+        r_s, t_s, summ = sorted(lm_runs, key=lambda q: q[2].seconds_total)[len(lm_runs) // 2]
     barrier()
     want_trial = world > 1 and not a.no_peer_trial and (a.peer_trial or os.environ.get("SBA_BENCH_PEER_TRIAL", "0") == "1")
     trial = None
@@ -865,9 +899,6 @@ def main():
     if rank == 0:
         total = a.n * world
         value = total * a.steps / elapsed
-        achieved = a.n * bytes_per_eval / (sweep_ms * 1e-3) / 1e9
-        kernel_sig = (f"sweep_kernel<{mode}, {depth_mode}, {'double' if a.store == 'f64' else 'float'}, "
-                      f"{1 if a.kernel == 'explicit' else 0}, true>")
         out = {
             "metric": "residual+Jacobian evals/sec", "value": value, "unit": "evals/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
@@ -884,6 +915,20 @@ def main():
                        "correspondences_per_gpu": a.n, "mode": a.workload, "storage": a.store,
                        "bytes_per_eval": bytes_per_eval, "allreduce": transport, "kernel": a.kernel,
                        "step": "sweep kernel + finalize kernel + all-reduce(24 f64, N>1) + pack published to the host and awaited"},
+            "preconditioning": {**precond, "what": "un-timed sweeps of the same kernel before the warm-up steps "
+                                                   "(clock dip after the first ~1.5 ms of load; --precondition-ms)",
+                                # everything the device ran between the upload and the first timed step
+                                "launches_before_the_timed_region": precond["sweeps"] + a.warmup
+                                                                    + (0 if cold is None else a.warmup + a.steps)},
+            "peer_trial": trial,
+            "upload_s": upload_s,   # once per problem (H2D over PCIe + re-layout); never part of `value`
+            "cost": float(pack[22]),
+        }
+    if rank == 0 and a.full:
+        achieved = a.n * bytes_per_eval / (sweep_ms * 1e-3) / 1e9
+        kernel_sig = (f"sweep_kernel<{mode}, {depth_mode}, {'double' if a.store == 'f64' else 'float'}, "
+                      f"{1 if a.kernel == 'explicit' else 0}, true>")
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": pmc_traffic(kernel_sig, a.n),
                          "traffic_source": "profiles/pmc_latest.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes "
@@ -895,11 +940,6 @@ def main():
                          "kernel_ms_max": float(per_launch.max()),
                          "kernel_ms_per_launch": [round(float(x), 4) for x in per_launch[:32]],
                          "algorithmic_bytes_per_launch": a.n * bytes_per_eval},
-            "preconditioning": {**precond, "what": "un-timed sweeps of the same kernel before the warm-up steps "
-                                                   "(clock dip after the first ~1.5 ms of load; --precondition-ms)",
-                                # everything the device ran between the upload and the first timed step
-                                "launches_before_the_timed_region": precond["sweeps"] + a.warmup
-                                                                    + (0 if cold is None else a.warmup + a.steps)},
             "cold": cold,
             "kernel_only_evals_per_s": a.n / (sweep_ms * 1e-3),
             "device_step_ms": step_ms,
@@ -907,11 +947,8 @@ def main():
                    "what": "median of 7 solves", "iterations": summ.num_iterations, "termination": summ.termination,
                    "rot_err_rad": float(np.abs(r_s - c.rot_true).max()),
                    "tran_err": float(np.abs(t_s - c.tran_true).max())},
-            "peer_trial": trial,
-            "upload_s": upload_s,   # once per problem (H2D over PCIe + re-layout); never part of `value`
             "pcie_inclusive_evals_per_s_if_reuploaded_every_sweep": a.n / (upload_s + elapsed / a.steps),
-            "cost": float(pack[22]),
-        }
+        })
         if world == 1 and not rehearsal and bytes_per_eval == 64 and a.store == "f64":
             probe = stream_probe(a.n)
             if probe:
@@ -924,7 +961,6 @@ def main():
                             "kernel's access pattern and no residual/Jacobian arithmetic"}
         if not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(c, mode, rt, a.cpu_sample, a.cpu_seconds)
-    if rank == 0:
         if world == 1 and not rehearsal and rt and a.n == 10_000_000 and a.store == "f64" and not a.no_scaling_reference:
             out["scaling_reference"] = scaling_reference(api, synthetic, c, seed, device_index, a)
         if world == 1 and not rehearsal and not a.no_stage_leg and rt:
@@ -935,6 +971,7 @@ def main():
         if world == 1 and not rehearsal and not a.no_c5_leg and rt and a.store == "f64":
             p.close()                       # the child gets the GPU to itself
             out["c5"] = c5_leg(a.steps, a.warmup)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     p.close()
     if dist is not None:

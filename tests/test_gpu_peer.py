@@ -187,7 +187,8 @@ def test_bench_multi_rank_rehearsal(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "10", "--warmup",
            "2", "--matches", "200000", "--transport", "peer",    # RCCL (the default) cannot place two ranks on ONE device
-           "--peer-trial"]                                        # the un-quoted second measurement is opt-in
+           "--peer-trial",                                        # the un-quoted second measurement is opt-in
+           "--full"]                                              # cold leg, roofline and LM figures
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -210,7 +211,7 @@ def test_bench_multi_rank_rehearsal(tmp_path):
 
 def test_bench_four_rank_rehearsal_default_flags(tmp_path):
     """The driver's own N = 4 command line (no transport / trial flags) in the one-GPU rehearsal mode, except that the
-    transport must be named: RCCL cannot place several ranks on one device.  Four ranks + this process = 5 processes on
+    transport must be named: RCCL cannot place several ranks on one device, and `--full` asks for the LM figure.  Four ranks + this process = 5 processes on
     the card (the pool admits 6), so the node's width of 8 cannot be rehearsed as processes -- the 8-rank exchange is
     covered by test_peer_exchange_processes_on_one_gpu[4-2].  No peer trial unless asked for."""
     import json
@@ -221,7 +222,7 @@ def test_bench_four_rank_rehearsal_default_flags(tmp_path):
     env = dict(os.environ, SBA_BENCH_ONE_GPU="1", SBA_TRANSPORT="peer")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "4", "--steps", "10", "--warmup",
-           "2", "--matches", "100000"]
+           "2", "--matches", "100000", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -243,7 +244,8 @@ def test_bench_c5_two_rank_rehearsal(tmp_path):
     env = dict(os.environ, SBA_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "5", "--warmup",
-           "1", "--workload", "c5", "--pairs", "256", "--pair-matches", "2000", "--frames", "2", "--precondition-ms", "5"]
+           "1", "--workload", "c5", "--pairs", "256", "--pair-matches", "2000", "--frames", "2", "--precondition-ms", "5",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -175,14 +175,14 @@ def test_resident_kernel_survives_an_idle_host(oracle, monkeypatch):
 
 
 def test_bench_default_line_carries_roofline_cpu_baseline_and_c5(tmp_path):
-    """`python bench.py` as the driver runs it at N = 1 (smaller problem, same code path): ONE JSON line with the contract's
+    """`python bench.py --full` at N = 1 (smaller problem, same code path): ONE JSON line with the contract's
     keys, `roofline` and `cpu_baseline`, and the config-C5 figures from the child run (`c5`)."""
     import json
     import subprocess
     import sys
     from helpers import ROOT
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--matches", "300000", "--steps", "5", "--warmup", "2",
-                        "--cpu-seconds", "1", "--cpu-sample", "100000", "--precondition-ms", "5"],
+                        "--cpu-seconds", "1", "--cpu-sample", "100000", "--precondition-ms", "5", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=tmp_path)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -215,3 +215,47 @@ def test_bench_default_line_carries_roofline_cpu_baseline_and_c5(tmp_path):
     assert b["cold"]["value"] > 0
     c2 = b["c2"]
     assert c2["ok"] and c2["lm"]["termination"].startswith("CONVERGENCE") and 0.1 < c2["roofline"]["frac"] < 1.0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` run times the K steps and prints the headline line only (the secondary figures are
+    `--full`'s), and `--dump-outputs` writes the last timed step's pack: the same pack this process computes from the
+    same seeded workload.  `--workload c5` likewise, one pack per pair."""
+    import json
+    import subprocess
+    import sys
+    from helpers import REL_TOL_F64, ROOT
+    n = 300_000
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--matches", str(n), "--steps", "7", "--warmup", "2",
+                        "--precondition-ms", "5", "--dump-outputs", str(tmp_path / "rt")],
+                       capture_output=True, text=True, timeout=300, cwd=tmp_path)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    b = json.loads(lines[0])
+    assert b["metric"] == "residual+Jacobian evals/sec" and b["unit"] == "evals/s" and b["higher_is_better"] is True
+    assert b["dtype"] == "f64" and b["steps"] == 7 and b["warmup"] == 2
+    assert abs(b["value"] - n * 7 / (b["ms_per_step"] * 1e-3 * 7)) <= 1e-6 * b["value"]
+    for key in ("roofline", "cold", "lm", "cpu_baseline", "scaling_reference", "stages", "c1", "c2", "c5"):
+        assert key not in b, key
+    got = np.load(tmp_path / "rt" / "pack.npy")
+    assert got.dtype == np.float64 and got.shape == (24,) and got[22] == b["cost"]
+    c = synthetic.full_rt(n, seed=synthetic.BASE_SEED + 2, shard=0)        # bench.py's workload at N = 1
+    with api.Problem(0) as p:
+        p.upload(c.x1, c.x2, c.d12)
+        want, _ = p.eval_steps(api.MODE_RT, c.rot_init, c.tran_init, depth_mode=api.DEPTH_PER_MATCH, steps=1)
+    assert np.abs(got - want).max() <= REL_TOL_F64 * np.abs(want).max()
+
+    B, m = 8, 2000
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--workload", "c5", "--pairs", str(B), "--pair-matches", str(m),
+                        "--steps", "3", "--warmup", "1", "--precondition-ms", "5", "--dump-outputs", str(tmp_path / "c5")],
+                       capture_output=True, text=True, timeout=300, cwd=tmp_path)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    b = json.loads(lines[0])
+    assert b["steps"] == 3 and abs(b["value"] - B * m * 3 / (b["ms_per_step"] * 1e-3 * 3)) <= 1e-6 * b["value"]
+    for key in ("roofline", "lm", "depth_stage", "pipeline", "equi2cube", "cpu_baseline"):
+        assert key not in b, key
+    packs = np.load(tmp_path / "c5" / "packs.npy")
+    assert packs.dtype == np.float64 and packs.shape == (B, 24) and np.isfinite(packs).all() and (packs[:, 22] > 0).all()

@@ -1,5 +1,5 @@
 import os, sys, time
-sys.path.insert(0,'/root/repo')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 from spherical_bundle_adjuster_amd import api, synthetic
 for n in (512, 1024, 2048, 2560, 4096, 6144, 8192, 12288, 16384, 32768):

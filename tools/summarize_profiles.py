@@ -134,7 +134,7 @@ def main():
     (out / "pmc_latest.json").write_text(json.dumps(summary, indent=1))
     lines = [f"# rocprofv3 summary {tag}", "",
              "Command (tools/profile_round.sh): `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 50 --warmup 5 "
-             "--no-cpu-baseline`, then separate `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` passes of the same command.", "",
+             "--full --no-cpu-baseline ...`, then separate `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` passes of the same command.", "",
              "| kernel | calls | avg us | min us | max us | FETCH_SIZE KiB | read bytes (x2, gfx950) | WRITE_SIZE KiB |",
              "|---|---|---|---|---|---|---|---|"]
     for k, r in stats.items():
