@@ -215,6 +215,11 @@ int sba_problem_set_depths(sba_problem* p, const double* d12);
 /* Select the sweep kernel (SBA_KERNEL_*); also settable with the environment variable
  * SBA_KERNEL=explicit at sba_problem_create time.                                                 */
 int sba_problem_set_kernel(sba_problem* p, int kind);
+/* on = 1 (default): sweeps with per-match depths over f64 planes stream X1 = d1 x1 and X2 = d2 x2, kept in six extra
+ * planes of the handle (48 B per match instead of 64; formed at upload / set_depths, re-formed before the next such sweep
+ * after the d-only stage).  on = 0: they stream the raw planes and the extra planes are released.  The results are the
+ * same bits either way; only speed and device memory differ.                                                           */
+int sba_problem_set_folding(sba_problem* p, int on);
 
 /* ---- one residual + Jacobian sweep ------------------------------------------------------ */
 /* Evaluates all local correspondences at (rot, tran), reduces on the device, all-reduces if a

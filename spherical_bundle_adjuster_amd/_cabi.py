@@ -95,6 +95,7 @@ SIGNATURES = {
     "sba_problem_upload_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int]),
     "sba_problem_size": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "sba_problem_set_kernel": (C.c_int, [_vp, C.c_int]),
+    "sba_problem_set_folding": (C.c_int, [_vp, C.c_int]),
     "sba_problem_set_depths": (C.c_int, [_vp, _vp]),
     "sba_problem_eval": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double,
                                    C.c_double, C.POINTER(NormalEq)]),

@@ -175,6 +175,11 @@ class Problem:
         """KERNEL_FACTORED (default) or KERNEL_EXPLICIT."""
         cabi.check(self._lib, self._lib.sba_problem_set_kernel(self._h, kind))
 
+    def set_folding(self, on: bool) -> None:
+        """Per-match-depth sweeps over f64 planes stream the depth-folded planes d1 x1, d2 x2 (True, default) or the
+        raw planes (False).  Same results either way."""
+        cabi.check(self._lib, self._lib.sba_problem_set_folding(self._h, 1 if on else 0))
+
     @property
     def size(self) -> int:
         n = C.c_size_t(0)

@@ -14,8 +14,8 @@ namespace sba {
 // Wave-uniform state of one sweep, passed BY VALUE as a kernel argument (kernarg segment ->
 // scalar loads), staged in LDS by the kernel prologue.
 //   uniform depths  : Rn = -d1 * R,  Gn_j = -d1 * dR/dw_j   (d1 folded in on the host)
-//   per-match depths: Rn = -R,       Gn_j = -dR/dw_j        (d1_i applied per match)
-// so that  e = t + d2 x2 + [d1_i] Rn x1   and   A = d(e)/d(rot) = [d1_i] [Gn_0 x1 | Gn_1 x1 | Gn_2 x1].
+//   per-match depths: Rn = -R,       Gn_j = -dR/dw_j        (d1_i applied per match: X1 = d1_i x1, X2 = d2_i x2)
+// so that  e = t + d2 x2 + Rn [d1_i] x1   and   A = d(e)/d(rot) = [Gn_0 X1 | Gn_1 X1 | Gn_2 X1].
 struct SweepParams {
   double Rn[9];
   double Gn[27];   // Gn[9*j + 3*r + c]
@@ -47,8 +47,8 @@ SBA_HD inline void fill_sweep_params(unsigned long long n, int depth_mode, const
 // Device-resident correspondences as planes (structure of arrays): every lane of a wave reads
 // 16 consecutive bytes of one plane, so each wave load instruction covers 1 KiB contiguous.
 struct Planes {
-  const void* x1[3];  // left unit vectors  x, y, z   (double or float per `store`)
-  const void* x2[3];  // right unit vectors x, y, z
+  const void* x1[3];  // left unit vectors  x, y, z   (double or float per `store`; folded sweeps: X1 = d1 x1)
+  const void* x2[3];  // right unit vectors x, y, z                               (folded sweeps: X2 = d2 x2)
   const double* d1;   // per-match depths (always f64), may be null
   const double* d2;
 };
@@ -75,7 +75,9 @@ struct SweepOut {
   unsigned long long seq;
 };
 
+constexpr int kDepthFolded = 2;   // launch_sweep's depth for per-match depths folded into f64 coordinate planes
 // kind: 0 = factored (moment pack, host applies J_l), 1 = explicit per-match Jacobian (SBA_PACK layout).
+// depth: 0 uniform, 1 per match (8 planes), 2 per match folded into the coordinates (6 f64 planes, store 0 only).
 hipError_t launch_sweep(int mode, int depth, int store, int kind, const Planes& pl, const SweepParams& prm,
                         const SweepOut& out, int grid, hipStream_t stream);
 hipError_t sweep_blocks_per_cu(int mode, int depth, int store, int kind, bool loss, int* blocks);
@@ -213,6 +215,10 @@ hipError_t launch_batch_d12_to_planes(const double* d12, size_t m, size_t first_
                                       hipStream_t stream);
 hipError_t launch_planes_to_d12(const double* d1, const double* d2, size_t n, double* d12,
                                 hipStream_t stream);
+// f64 planes of `elems` elements (a multiple of 2): folded[0..2] = d1 * coord[0..2], folded[3..5] = d2 * coord[3..5].
+// grid_cap: most blocks of 256 threads (grid-stride beyond).
+hipError_t launch_fold_depths(const void* const coord[6], const double* d1, const double* d2, double* const folded[6],
+                              size_t elems, int grid_cap, hipStream_t stream);
 
 // d-only stage (spherical_bundle_adjuster.cpp:1004-1063): one LM iteration of the global bounded problem.
 struct DepthParams {

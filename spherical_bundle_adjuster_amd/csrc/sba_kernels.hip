@@ -4,15 +4,15 @@
 // blocks (reference spherical_bundle_adjuster.cpp:843-868, :891-919, :947-976 evaluated through
 // AutoDiffCostFunction + HuberLoss(1.0), :887/:943/:1000).  Per correspondence i ("one evaluation"):
 //
-//       v  = d1 Rn x1_i            (Rn = -R, or -d1 R with uniform depths)
-//       e  = t + d2 x2_i + v                                   residual            (.cpp:897-916)
+//       v  = Rn X1_i               (Rn = -R, X1_i = d1_i x1_i; or Rn = -d1 R, X1_i = x1_i with uniform depths)
+//       e  = v + (X2_i + t)        (X2_i = d2_i x2_i)          residual            (.cpp:897-916)
 //       s  = e.e ;  w = rho'(s) ;  rho(s)                      block-wise Huber (Ceres corrector with
 //                                                              rho'' <= 0: scale e and J by sqrt(w))
 //   KIND_FACTORED (default):  d e/d rot = A = -[v]x J_l(rot) with J_l constant per sweep, so the
 //       normal equations factor through moments of v and e; the kernel accumulates
 //           M = sum w v v^T (6), C = sum w v e^T (9), m = sum w v (3), sum w e (3), sum w, cost
 //       and the host applies J_l (sba_rotation.hpp: moments_to_normal_pack).
-//   KIND_EXPLICIT:  A = d1 [Gn_0 x1 | Gn_1 x1 | Gn_2 x1] formed per match (what Jet<double,3> carries),
+//   KIND_EXPLICIT:  A = [Gn_0 X1 | Gn_1 X1 | Gn_2 X1] formed per match (what Jet<double,3> carries),
 //           acc += w A^T A, w A^T, w, w A^T e, w e, rho/2
 //       kept as the independent cross-check of the factored form.
 //   wave:   DPP butterfly over the 64 lanes
@@ -21,8 +21,8 @@
 //
 // Memory: the coordinate planes are read exactly once, 16 B per lane per load instruction (1 KiB
 // contiguous per wave instruction), next vector prefetched into registers while the current one is
-// consumed.  No reuse, no MFMA: HBM-bound (48 B per evaluation with f64 planes and uniform depths,
-// 64 B with per-match depths).  The wave-uniform R|t state (SweepParams) is a by-value kernel argument:
+// consumed.  No reuse, no MFMA: HBM-bound (48 B per evaluation with f64 planes and uniform depths or per-match
+// depths folded into the coordinates -- DEPTH_FOLDED, the default for f64 planes -- 64 B from the raw per-match planes).  The wave-uniform R|t state (SweepParams) is a by-value kernel argument:
 // scalar loads, operands stay in SGPRs (SBA_PARAMS_IN_LDS=1 stages it in LDS instead).
 //
 // This file: the single-problem sweep kernel, the final reduction / peer exchange / host hand-over kernels and their
@@ -330,6 +330,15 @@ SweepFn pick_store(int store, int kind, bool loss) {
   return store == 0 ? pick_kind<MODE, DEPTH, double>(kind, loss) : pick_kind<MODE, DEPTH, float>(kind, loss);
 }
 SweepFn pick(int mode, int depth, int store, int kind, bool loss) {
+  if (depth == DEPTH_FOLDED) {   // f64 planes only: f32 X1 / X2 would round the products the raw path keeps in f64
+    if (store != 0) return nullptr;
+    switch (mode) {
+      case MODE_ROT: return pick_kind<MODE_ROT, DEPTH_FOLDED, double>(kind, loss);
+      case MODE_TRAN: return pick_kind<MODE_TRAN, DEPTH_FOLDED, double>(KIND_FACTORED, loss);
+      case MODE_RT: return pick_kind<MODE_RT, DEPTH_FOLDED, double>(kind, loss);
+    }
+    return nullptr;
+  }
   switch (mode * 2 + depth) {
     case 0: return pick_store<MODE_ROT, DEPTH_UNIFORM>(store, kind, loss);
     case 1: return pick_store<MODE_ROT, DEPTH_PER_MATCH>(store, kind, loss);

@@ -26,7 +26,7 @@ struct sba_problem {
                                // (1 or 2: the register double buffer supplies the memory-level parallelism, more
                                // waves only add rows to fold and finish-time spread, profiles/r01_tune_caps.log)
   int kind = SBA_KERNEL_FACTORED;
-  int occ_cache[3][2][2][2][2];  // resident blocks/CU per [mode][depth][store][kind][loss], 0 = unknown
+  int occ_cache[3][3][2][2][2];  // resident blocks/CU per [mode][depth (2 = folded)][store][kind][loss], 0 = unknown
   int depth_occ[2] = {0, 0};     // same for depth_step_kernel per [store]
   double* epi_scratch = nullptr; // 8-point moments: [grid][45][64] block partials + [64][45] groups, kept across calls
   size_t epi_scratch_elems = 0;
@@ -45,9 +45,19 @@ struct sba_problem {
   size_t plane_elems = 0;     // allocated elements per plane (n rounded up to a whole vector)
   void* coord[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double* dplane[2] = {nullptr, nullptr};
-  void* plane_base[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // hipMalloc'ed blocks
-  size_t plane_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // their sizes: an upload that fits reuses them (a hipFree + hipMalloc pair per
-                                                      // plane costs more than the whole upload of a 2 000-match problem)
+  // Per-match depths folded into the coordinates, X1 = d1 x1 and X2 = d2 x2 (f64 planes only): a cache of the raw planes
+  // that per-match sweeps stream instead of them -- 48 B per match instead of 64.  The raw planes
+  // stay: the d-only stage, the initial guess and the batched / resident paths read them.  Refolded at the end of every
+  // upload / set_depths; writers on the device (the d-only stage) only clear folded_valid, and the next per-match sweep
+  // refolds first.
+  double* folded[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool folding = true;         // sba_problem_set_folding
+  bool folded_valid = false;   // folded[] hold d1 x1, d2 x2 of the current planes
+  bool fold_failed = false;    // their allocation failed for this upload: per-match sweeps read the raw planes
+  static constexpr int kPlaneSlots = 14;   // 6 coordinate + 2 depth planes, then the 6 folded planes
+  void* plane_base[kPlaneSlots] = {};      // hipMalloc'ed blocks
+  size_t plane_bytes[kPlaneSlots] = {};    // their sizes: an upload that fits reuses them (a hipFree + hipMalloc pair per
+                                           // plane costs more than the whole upload of a 2 000-match problem)
   size_t plane_stagger = 4352; // SBA_PLANE_STAGGER: plane k starts k * 4352 B (17 x 256 B) into its allocation, so equal
                                // element indices of the 8 streams differ in their low address bits (measured 0-4 %
                                // faster with f64 planes, 3-5 % with f32 planes; never slower)

@@ -231,13 +231,15 @@ using sba::shim::rccl;
 namespace {
 
 int free_planes(sba_problem* p) {
-  for (int k = 0; k < 8; ++k) {
+  for (int k = 0; k < sba_problem::kPlaneSlots; ++k) {
     if (p->plane_base[k]) SBA_HIP_TRY(hipFree(p->plane_base[k]));
     p->plane_base[k] = nullptr;
     p->plane_bytes[k] = 0;
   }
   for (auto& c : p->coord) c = nullptr;
   for (auto& d : p->dplane) d = nullptr;
+  for (auto& f : p->folded) f = nullptr;
+  p->folded_valid = false;
   p->uploaded = false;
   p->n = 0;
   p->plane_elems = 0;
@@ -259,8 +261,26 @@ int ensure_plane(sba_problem* p, int k, size_t bytes) {
   return SBA_OK;
 }
 
+// The folded planes (slots 8..13) go back to the device.
+int release_folded(sba_problem* p) {
+  p->folded_valid = false;
+  for (int k = 8; k < sba_problem::kPlaneSlots; ++k) {
+    if (p->plane_base[k]) SBA_HIP_TRY(hipFree(p->plane_base[k]));
+    p->plane_base[k] = nullptr;
+    p->plane_bytes[k] = 0;
+  }
+  for (auto& f : p->folded) f = nullptr;
+  return SBA_OK;
+}
+
 int alloc_planes(sba_problem* p, size_t n, bool with_d12, int store) {
   p->uploaded = false;
+  p->folded_valid = false;
+  p->fold_failed = false;
+  if (!with_d12 || store != SBA_STORE_F64) {
+    const int rc = release_folded(p);
+    if (rc) return rc;
+  }
   const size_t esz = store == SBA_STORE_F64 ? 8 : 4;
   // whole 16-byte vectors, plus one spare vector so that the ragged tail load stays in bounds
   const size_t ppt = static_cast<size_t>(sba::points_per_lane(store));
@@ -290,7 +310,68 @@ int alloc_planes(sba_problem* p, size_t n, bool with_d12, int store) {
   return SBA_OK;
 }
 
-// One resident wave of blocks: min(blocks needed, CUs x resident blocks per CU of this kernel).
+}  // namespace
+namespace sba {
+// Referenced weakly: the host translation units are also linked on their own against a mock device (tests/harness), whose
+// stub launchers predate this one.  Without it a handle simply sweeps the raw planes.  The library always defines it.
+hipError_t launch_fold_depths(const void* const coord[6], const double* d1, const double* d2, double* const folded[6],
+                              size_t elems, int grid_cap, hipStream_t stream) __attribute__((weak));
+}  // namespace sba
+namespace {
+
+bool fold_eligible(const sba_problem* p) {
+  return p->folding && p->uploaded && p->has_d12 && p->store == SBA_STORE_F64 && !p->fold_failed;
+}
+
+// Bring the folded planes up to date (enqueued on the problem's stream): X1 = d1 x1, X2 = d2 x2 over the whole allocated
+// length, so the zero padding of the raw planes carries over.  Same sizes and stagger as the coordinate planes.  If they
+// cannot be allocated the handle keeps sweeping the raw planes -- the same bits, only slower -- until the next upload.
+int ensure_folded(sba_problem* p) {
+  if (p->folded_valid || !fold_eligible(p)) return SBA_OK;
+  if (!sba::launch_fold_depths) { p->fold_failed = true; return SBA_OK; }
+  const size_t bytes = p->plane_elems * sizeof(double) + 8 * p->plane_stagger;
+  for (int j = 0; j < 6; ++j) {
+    const int k = 8 + j;
+    if (!p->plane_base[k] || p->plane_bytes[k] < bytes || p->plane_bytes[k] > 4 * bytes + (size_t(1) << 20)) {
+      if (p->plane_base[k]) SBA_HIP_TRY(hipFree(p->plane_base[k]));
+      p->plane_base[k] = nullptr;
+      p->plane_bytes[k] = 0;
+      if (hipMalloc(&p->plane_base[k], bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        p->fold_failed = true;
+        return release_folded(p);
+      }
+      p->plane_bytes[k] = bytes;
+    }
+    p->folded[j] = reinterpret_cast<double*>(static_cast<char*>(p->plane_base[k]) + j * p->plane_stagger);
+  }
+  SBA_HIP_TRY(sba::launch_fold_depths(p->coord, p->dplane[0], p->dplane[1], p->folded, p->plane_elems, p->num_cus * 8,
+                                      p->stream));
+  p->folded_valid = true;
+  return SBA_OK;
+}
+
+// The planes a single-problem sweep streams and the kernel variant (launch_sweep's depth) that reads them: per-match
+// depths on f64 planes sweep the folded planes (refolded first if a writer invalidated them), anything else the raw ones.
+int sweep_planes(sba_problem* p, int depth_mode, sba::Planes* pl, int* kernel_depth) {
+  bool folded = false;
+  if (depth_mode == SBA_DEPTH_PER_MATCH && fold_eligible(p)) {
+    const int rc = ensure_folded(p);
+    if (rc) return rc;
+    folded = p->folded_valid;
+  }
+  for (int k = 0; k < 3; ++k) {
+    pl->x1[k] = folded ? p->folded[k] : p->coord[k];
+    pl->x2[k] = folded ? p->folded[3 + k] : p->coord[3 + k];
+  }
+  pl->d1 = folded ? nullptr : p->dplane[0];
+  pl->d2 = folded ? nullptr : p->dplane[1];
+  *kernel_depth = folded ? sba::kDepthFolded : depth_mode;
+  return SBA_OK;
+}
+
+// One resident wave of blocks: min(blocks needed, CUs x resident blocks per CU of this kernel).  depth_mode: launch_sweep's
+// depth (sba::kDepthFolded for the folded planes).
 int grid_for(sba_problem* p, int mode, int depth_mode, bool loss, int* grid) {
   const size_t ppt = static_cast<size_t>(sba::points_per_lane(p->store));
   const size_t nvec = (p->n + ppt - 1) / ppt;
@@ -303,7 +384,9 @@ int grid_for(sba_problem* p, int mode, int depth_mode, bool loss, int* grid) {
     // A/B on one box): the f64 factored kernel streaming 8 planes (R|t with per-match depths: 96.7 / 96.7 / 95.3 us at
     // one block per CU against 99.6 / 99.0 / 97.4 us at two) and its tran-only form finish tighter with ONE block per
     // CU -- fewer resident blocks, less finish-time spread between XCDs (profiles/r01_stream_probe.md) -- every other
-    // variant (6 planes, f32 planes, explicit Jacobian) needs the second block to cover its arithmetic.
+    // variant (6 planes, f32 planes, explicit Jacobian) needs the second block to cover its arithmetic.  The folded
+    // per-match R|t variant (6 planes) among them: 86.9 / 87.2 us per step at two blocks per CU against 90.4 / 90.5 us at
+    // one (profiles/fold_ab.log).
     int cap = p->blocks_per_cu_cap;
     if (cap <= 0)
       cap = (p->store == SBA_STORE_F64 && p->kind == SBA_KERNEL_FACTORED &&
@@ -343,14 +426,10 @@ void make_frame(sba_problem* p, int mode, const double rot[3]) {
 // Enqueue one sweep + finalize (+ all-reduce) on the problem's stream; pack_dev holds the result.
 int enqueue_sweep(sba_problem* p, int mode, int depth_mode, const sba::SweepParams& prm) {
   sba::Planes pl;
-  for (int k = 0; k < 3; ++k) {
-    pl.x1[k] = p->coord[k];
-    pl.x2[k] = p->coord[3 + k];
-  }
-  pl.d1 = p->dplane[0];
-  pl.d2 = p->dplane[1];
+  int rc0 = sweep_planes(p, depth_mode, &pl, &depth_mode);
+  if (rc0) return rc0;
   int grid = 0;
-  int rc0 = grid_for(p, mode, depth_mode, prm.delta > 0.0, &grid);
+  rc0 = grid_for(p, mode, depth_mode, prm.delta > 0.0, &grid);
   if (rc0) return rc0;
   // Final reduction + hand-over.  Default: the sweep stays a pure streaming kernel and a one-block finalize kernel
   // folds the block rows and publishes the pack into mapped pinned host memory, followed by a sequence number the
@@ -675,8 +754,10 @@ static int upload_common(sba_problem* p, const void* left, const void* right, co
       SBA_SYNC(p, "upload");      // before the staging buffer goes out of scope
     }
   }
-  SBA_SYNC(p, "stream synchronisation");
   p->uploaded = true;
+  rc = ensure_folded(p);
+  if (rc) return rc;
+  SBA_SYNC(p, "stream synchronisation");
   return SBA_OK;
 }
 
@@ -730,14 +811,31 @@ int sba_problem_set_depths(sba_problem* p, const double* d12) {
     }
     p->has_d12 = true;
   }
+  p->folded_valid = false;
   if (p->n > 0) {
     sba::DeviceBuffer stage(&p->poisoned);
     SBA_HIP_TRY(stage.alloc(p->n * 2 * sizeof(double)));
     SBA_HIP_TRY(hipMemcpyAsync(stage.ptr, d12, p->n * 2 * sizeof(double), hipMemcpyHostToDevice, p->stream));
     SBA_HIP_TRY(sba::launch_d12_to_planes(stage.as<double>(), p->n, 0, p->dplane[0], p->dplane[1], p->stream));
+    const int rc = ensure_folded(p);
+    if (rc) return rc;
     SBA_SYNC(p, "stream synchronisation");
   }
   return SBA_OK;
+}
+
+int sba_problem_set_folding(sba_problem* p, int on) {
+  if (!p) return fail(SBA_ERR_INVALID_ARG, "null problem handle");
+  SBA_REFUSE_POISONED(p);
+  if (on == 0 || on == 1) {
+    p->folding = on != 0;
+  } else {
+    return fail(SBA_ERR_INVALID_ARG, "bad folding switch %d (0 or 1)", on);
+  }
+  if (p->folding) return SBA_OK;                   // folded lazily before the next per-match sweep
+  SBA_HIP_TRY(hipSetDevice(p->device));
+  SBA_SYNC(p, "stream synchronisation");           // a sweep may still read the folded planes
+  return release_folded(p);
 }
 
 int sba_problem_set_kernel(sba_problem* p, int kind) {
@@ -822,17 +920,18 @@ int sba_problem_eval_timed(sba_problem* p, int mode, int depth_mode, const doubl
   if (mean_sweep_ms) {
     // the sweep kernel alone: `repeat` launches back to back under ONE event pair (kernel + the ~1.5 us boundary
     // between dependent launches; per-launch event brackets would add another 2-4 us each)
-    int grid = 0;
-    rc = grid_for(p, mode, depth_mode, prm.delta > 0.0, &grid);
-    if (rc) return rc;
     sba::Planes pl;
-    for (int k = 0; k < 3; ++k) { pl.x1[k] = p->coord[k]; pl.x2[k] = p->coord[3 + k]; }
-    pl.d1 = p->dplane[0]; pl.d2 = p->dplane[1];
+    int kdepth = depth_mode;
+    rc = sweep_planes(p, depth_mode, &pl, &kdepth);
+    if (rc) return rc;
+    int grid = 0;
+    rc = grid_for(p, mode, kdepth, prm.delta > 0.0, &grid);
+    if (rc) return rc;
     sba::SweepOut out;
     out.partials = p->partials; out.pack_dev = p->pack_dev; out.pack_host = nullptr; out.ticket = nullptr; out.seq = 0;
     SBA_HIP_TRY(hipEventRecord(p->ev0, p->stream));
     for (int i = 0; i < repeat; ++i)
-      SBA_HIP_TRY(sba::launch_sweep(mode, depth_mode, p->store, p->kind, pl, prm, out, grid, p->stream));
+      SBA_HIP_TRY(sba::launch_sweep(mode, kdepth, p->store, p->kind, pl, prm, out, grid, p->stream));
     SBA_HIP_TRY(hipEventRecord(p->ev1, p->stream));
     SBA_HIP_TRY(hipEventSynchronize(p->ev1));
     SBA_HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
@@ -863,12 +962,13 @@ int sba_problem_eval_launch_times(sba_problem* p, int mode, int depth_mode, cons
   sba::SweepParams prm;
   make_params(p, depth_mode, rot, tran, d1, d2, huber_delta, &prm);
   make_frame(p, mode, rot);
-  int grid = 0;
-  rc = grid_for(p, mode, depth_mode, prm.delta > 0.0, &grid);
-  if (rc) return rc;
   sba::Planes pl;
-  for (int k = 0; k < 3; ++k) { pl.x1[k] = p->coord[k]; pl.x2[k] = p->coord[3 + k]; }
-  pl.d1 = p->dplane[0]; pl.d2 = p->dplane[1];
+  int kdepth = depth_mode;
+  rc = sweep_planes(p, depth_mode, &pl, &kdepth);
+  if (rc) return rc;
+  int grid = 0;
+  rc = grid_for(p, mode, kdepth, prm.delta > 0.0, &grid);
+  if (rc) return rc;
   sba::SweepOut out;
   out.partials = p->partials; out.pack_dev = p->pack_dev; out.pack_host = nullptr; out.ticket = nullptr; out.seq = 0;
   // one event between every two launches: launch i runs between events i and i + 1
@@ -880,7 +980,7 @@ int sba_problem_eval_launch_times(sba_problem* p, int mode, int depth_mode, cons
   for (hipEvent_t& e : events.ev) SBA_HIP_TRY(hipEventCreate(&e));
   SBA_HIP_TRY(hipEventRecord(events.ev[0], p->stream));
   for (int i = 0; i < repeat; ++i) {
-    SBA_HIP_TRY(sba::launch_sweep(mode, depth_mode, p->store, p->kind, pl, prm, out, grid, p->stream));
+    SBA_HIP_TRY(sba::launch_sweep(mode, kdepth, p->store, p->kind, pl, prm, out, grid, p->stream));
     SBA_HIP_TRY(hipEventRecord(events.ev[static_cast<size_t>(i) + 1], p->stream));
   }
   SBA_HIP_TRY(hipEventSynchronize(events.ev[static_cast<size_t>(repeat)]));

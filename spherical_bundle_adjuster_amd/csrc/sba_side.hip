@@ -1,5 +1,7 @@
 // Kernels either side of the sweep: AoS -> plane re-layout at upload time, pixel -> unit sphere (reference
 // spherical_bundle_adjuster.cpp:271-298), and their launchers.  (The image / key-point maps live in sba_maps.hip.)
+#include <algorithm>
+
 #include "sba_device.hpp"
 
 namespace sba {
@@ -111,7 +113,42 @@ __global__ void keypoints_to_planes_kernel(const uint8_t* __restrict__ kp_left, 
   x2x[i] = static_cast<ST>(s2 * cos(lon2)); x2y[i] = static_cast<ST>(s2 * sin(lon2)); x2z[i] = static_cast<ST>(cos(col2));
 }
 
+// Per-match depths folded into the coordinates: X1 = d1 x1, X2 = d2 x2 (the rounded products the per-match sweep forms,
+// sba_sweep_core.hpp: accumulate), 16 B per lane per plane over the whole allocation -- the zero padding of the raw planes
+// becomes the zero padding of the folded ones.
+struct FoldPlanes {
+  const double* x[6];
+  const double* d[2];
+  double* X[6];
+};
+__global__ __launch_bounds__(256) void fold_depths_kernel(FoldPlanes f, size_t nvec) {
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const double2 d = reinterpret_cast<const double2*>(f.d[s])[i];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double2 c = reinterpret_cast<const double2*>(f.x[3 * s + k])[i];
+        reinterpret_cast<double2*>(f.X[3 * s + k])[i] = make_double2(d.x * c.x, d.y * c.y);
+      }
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t launch_fold_depths(const void* const coord[6], const double* d1, const double* d2, double* const folded[6],
+                              size_t elems, int grid_cap, hipStream_t stream) {
+  const size_t nvec = elems / 2;
+  if (nvec == 0) return hipSuccess;
+  FoldPlanes f;
+  for (int k = 0; k < 6; ++k) { f.x[k] = static_cast<const double*>(coord[k]); f.X[k] = folded[k]; }
+  f.d[0] = d1; f.d[1] = d2;
+  const unsigned grid = static_cast<unsigned>(std::min<size_t>((nvec + 255) / 256, static_cast<size_t>(std::max(grid_cap, 1))));
+  hipLaunchKernelGGL(fold_depths_kernel, dim3(grid), dim3(256), 0, stream, f, nvec);
+  return hipGetLastError();
+}
 
 hipError_t launch_aos_to_planes(const double* aos, size_t n, size_t first, void* px, void* py,
                                 void* pz, int store, hipStream_t stream, size_t tile_elems, size_t tile_stride_elems) {

@@ -33,6 +33,7 @@ int sba_problem_solve_depths(sba_problem* p, const double rot[3], const double t
     return sba::set_error(SBA_ERR_UNSUPPORTED, "d-only stage over a transport needs 1..8 shards (sba_problem_set_shard); have %d/%d",
                 p->shard_rank, p->shard_count);
   SBA_TRY_HIP(hipSetDevice(p->device));
+  p->folded_valid = false;     // every driver below rewrites the depth planes: the next per-match sweep refolds
   sba_lm_options o;
   if (opt) o = *opt; else sba::lm_default_options(&o);
   sba_lm_summary local;

@@ -19,6 +19,9 @@ namespace {
 
 constexpr int MODE_ROT = 0, MODE_TRAN = 1, MODE_RT = 2;
 constexpr int DEPTH_UNIFORM = 0, DEPTH_PER_MATCH = 1;
+// Per-match depths folded into the coordinates: the planes hold X1 = d1 x1 and X2 = d2 x2 (6 f64 planes, 48 B per match
+// instead of 64).  Single-problem sweep kernels only, f64 planes only.
+constexpr int DEPTH_FOLDED = kDepthFolded;
 constexpr int KIND_FACTORED = 0, KIND_EXPLICIT = 1;
 
 // ---- accumulator <-> pack slot maps -------------------------------------------------------
@@ -90,7 +93,7 @@ struct VecRegs {
       c[k] = stream_load(reinterpret_cast<const typename Lanes<ST>::vec*>(pl.x1[k]) + p);
       c[3 + k] = stream_load(reinterpret_cast<const typename Lanes<ST>::vec*>(pl.x2[k]) + p);
     }
-    if (DEPTH == DEPTH_PER_MATCH) {
+    if (DEPTH == DEPTH_PER_MATCH) {   // DEPTH_FOLDED: the six planes already carry the depths
 #pragma unroll
       for (int h = 0; h < PPT / 2; ++h) {
         d1[h] = stream_load(reinterpret_cast<const double2*>(pl.d1) + p * (PPT / 2) + h);
@@ -123,19 +126,32 @@ __device__ __forceinline__ void huber(double s, double delta, double delta2, dou
 }
 
 // ---- one correspondence ------------------------------------------------------------------------
+// A product that is rounded on its own: never contracted into an FMA with the sum it feeds.
+__device__ __forceinline__ double mul_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// Per-match depths follow the reference's order (every cost functor of spherical_bundle_adjuster.cpp: X1 = cam1 d1,
+// X2 = cam2 d2, then R X1): the rounded products X1 = d1 x1 and X2 = d2 x2 first, then v = Rn X1 and e = v + (X2 + t).
+// DEPTH_FOLDED loads X1, X2 as stored by fold_depths_kernel (sba_side.hip) -- the same rounded products -- so both forms
+// give the same bits per match.
 template <int MODE, int DEPTH, int KIND, bool LOSS>
 __device__ __forceinline__ void accumulate(const SweepParams* __restrict__ P, double x, double y,
                                            double z, double u, double v, double q, double d1, double d2,
                                            bool valid, double* __restrict__ acc) {
-  double r0 = P->Rn[0] * x + P->Rn[1] * y + P->Rn[2] * z;
-  double r1 = P->Rn[3] * x + P->Rn[4] * y + P->Rn[5] * z;
-  double r2 = P->Rn[6] * x + P->Rn[7] * y + P->Rn[8] * z;
-  double e0, e1, e2;
   if (DEPTH == DEPTH_PER_MATCH) {
-    r0 *= d1; r1 *= d1; r2 *= d1;
-    e0 = r0 + __builtin_fma(d2, u, P->t[0]);
-    e1 = r1 + __builtin_fma(d2, v, P->t[1]);
-    e2 = r2 + __builtin_fma(d2, q, P->t[2]);
+    x = mul_rounded(d1, x); y = mul_rounded(d1, y); z = mul_rounded(d1, z);
+    u = mul_rounded(d2, u); v = mul_rounded(d2, v); q = mul_rounded(d2, q);
+  }
+  const double r0 = P->Rn[0] * x + P->Rn[1] * y + P->Rn[2] * z;
+  const double r1 = P->Rn[3] * x + P->Rn[4] * y + P->Rn[5] * z;
+  const double r2 = P->Rn[6] * x + P->Rn[7] * y + P->Rn[8] * z;
+  double e0, e1, e2;
+  if (DEPTH != DEPTH_UNIFORM) {
+    e0 = r0 + (u + P->t[0]);
+    e1 = r1 + (v + P->t[1]);
+    e2 = r2 + (q + P->t[2]);
   } else {
     e0 = r0 + __builtin_fma(P->d2, u, P->t[0]);
     e1 = r1 + __builtin_fma(P->d2, v, P->t[1]);
@@ -190,16 +206,13 @@ __device__ __forceinline__ void accumulate(const SweepParams* __restrict__ P, do
     return;
   }
 
-  // KIND_EXPLICIT: A[r][j] = (Gn_j x1)[r]
+  // KIND_EXPLICIT: A[r][j] = (Gn_j X1)[r]  (X1 = x1 with uniform depths: d1 sits in Gn)
   double A[3][3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      double a = P->Gn[9 * j + 3 * r + 0] * x + P->Gn[9 * j + 3 * r + 1] * y +
-                 P->Gn[9 * j + 3 * r + 2] * z;
-      if (DEPTH == DEPTH_PER_MATCH) a *= d1;
-      A[r][j] = a;
+      A[r][j] = P->Gn[9 * j + 3 * r + 0] * x + P->Gn[9 * j + 3 * r + 1] * y + P->Gn[9 * j + 3 * r + 2] * z;
     }
   }
   double wA[3][3];
