@@ -454,7 +454,9 @@ int sba_batch_upload(sba_batch* b, const double* left_xyz, const double* right_x
   b->total_vecs = vec + 1;
   const size_t elems = b->total_vecs * ppt, esz = store == SBA_STORE_F64 ? 8 : 4;
   b->plane_elems = elems;
-  b->offsets.assign(offsets, offsets + num_pairs + 1);
+  // An empty batch may come without an offsets array (the argument check admits NULL for num_pairs == 0): keep {0}.
+  if (num_pairs == 0) b->offsets.assign(1, 0);
+  else b->offsets.assign(offsets, offsets + num_pairs + 1);
   for (int k = 0; k < 6; ++k) {
     const size_t lead = b->plane_stagger * static_cast<size_t>(k);
     SBA_TRY_HIP(hipMalloc(&b->plane_base[k], lead + elems * esz));

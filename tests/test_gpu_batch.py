@@ -665,6 +665,9 @@ def test_batch_errors_and_empty():
             b.eval(api.MODE_ROT, np.zeros((0, 3)), np.zeros((0, 3)))             # nothing uploaded
         b.upload(np.zeros((0, 3)), np.zeros((0, 3)), np.array([0], dtype=np.uint64))
         assert b.eval(api.MODE_ROT, np.zeros((0, 3)), np.zeros((0, 3))).shape == (0, 24)
+        # an empty batch without an offsets array (the header admits NULL for zero pairs): accepted, nothing read
+        assert b._lib.sba_batch_upload(b._h, None, None, None, None, 0, api.STORE_F64) == 0, cabi.last_error(b._lib)
+        assert b.eval(api.MODE_ROT, np.zeros((0, 3)), np.zeros((0, 3))).shape == (0, 24)
         c = synthetic.rotation_only(100, seed=1)
         b.upload(c.x1, c.x2, np.array([0, 40, 100], dtype=np.uint64))
         with pytest.raises(api.SbaError):
