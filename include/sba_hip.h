@@ -221,6 +221,26 @@ int sba_problem_set_kernel(sba_problem* p, int kind);
  * same bits either way; only speed and device memory differ.                                                           */
 int sba_problem_set_folding(sba_problem* p, int on);
 
+/* ---- single matches: residuals, inlier set, compaction ---- */
+/* e[i] = d2 x2 - d1 R(rot) x1 + tran, formed exactly as the sweep forms it (uniform depths d1, d2, or the per-match depths
+ * with depth_mode = SBA_DEPTH_PER_MATCH), for every uploaded match.  Every output may be NULL:
+ *   e_xyz   double[n][3]     the residual
+ *   sq_norm double[n]        s = e.e, the argument of the Huber loss
+ *   inlier  uint8[n]         !(s > huber_delta^2): 1 = inside Huber's quadratic region; all 1 when huber_delta <= 0
+ *   n_inlier                 the number of inliers; n - n_inlier equals SBA_PACK_NOUT of a sweep at the same arguments
+ * A match whose residual is NaN counts as an inlier here, as it does in the sweep's outlier count.  The residual does not
+ * depend on the sweep mode.  A sharded handle answers for its own matches.                                             */
+int sba_problem_residuals(sba_problem* p, int depth_mode, const double rot[3], const double tran[3], double d1, double d2,
+                          double huber_delta, double* e_xyz, double* sq_norm, unsigned char* inlier, size_t* n_inlier);
+/* Keep the matches with keep[i] != 0 (host array of the handle's size n), in their original order.  Afterwards the handle
+ * is what a fresh upload of the kept matches (coordinates and, if present, depths) with the same store would be: same size,
+ * same plane contents and padding, so every later sweep, solve, d-only stage, moment pass and initial guess gives the same
+ * bits as on such a handle; sba_problem_set_depths then takes *n_kept rows.  kept_index (may be NULL; capacity n) receives
+ * the *n_kept original indices in order.  Compacted on the device, deterministic; the count is the one synchronous step.
+ * A sharded handle compacts only its own matches: every rank of a collective may keep a different subset and the packs
+ * still sum over the union.  On an error the handle may be left without correspondences (SBA_ERR_NOT_UPLOADED after).  */
+int sba_problem_compact(sba_problem* p, const unsigned char* keep, size_t* n_kept, long long* kept_index);
+
 /* ---- one residual + Jacobian sweep ------------------------------------------------------ */
 /* Evaluates all local correspondences at (rot, tran), reduces on the device, all-reduces if a
  * communicator/hook is installed, and returns the expanded normal equations.  depth_mode

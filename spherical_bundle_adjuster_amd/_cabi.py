@@ -97,6 +97,9 @@ SIGNATURES = {
     "sba_problem_set_kernel": (C.c_int, [_vp, C.c_int]),
     "sba_problem_set_folding": (C.c_int, [_vp, C.c_int]),
     "sba_problem_set_depths": (C.c_int, [_vp, _vp]),
+    "sba_problem_residuals": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _dp, _vp,
+                                        C.POINTER(C.c_size_t)]),
+    "sba_problem_compact": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t), _vp]),
     "sba_problem_eval": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double,
                                    C.c_double, C.POINTER(NormalEq)]),
     "sba_problem_eval_pack": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double,

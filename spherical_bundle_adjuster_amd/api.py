@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import time
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -38,6 +39,14 @@ class SolveSummary:
     seconds_total: float
     seconds_eval: float
     num_line_search_steps: int = 0
+
+
+class Residuals(NamedTuple):
+    """Per-match residuals of a problem (Problem.residuals); a field that was not requested is None."""
+    e: np.ndarray | None          # (n, 3) e = d2 x2 - d1 R x1 + t
+    sq_norm: np.ndarray | None    # (n,)   e.e
+    inlier: np.ndarray | None     # (n,)   bool: inside Huber's quadratic region (NaN residuals count as inliers)
+    n_inlier: int
 
 
 def _f64(a, shape=None) -> np.ndarray:
@@ -231,6 +240,46 @@ class Problem:
         cabi.check(self._lib, self._lib.sba_problem_eval_steps(self._h, mode, depth_mode, _dptr(rot), _dptr(tran),
                                                                d1, d2, huber_delta, steps, _dptr(pack), C.byref(sec)))
         return pack, sec.value
+
+    # -- single matches ---------------------------------------------------------------------------------
+    def residuals(self, rot, tran, d1=1.0, d2=1.0, huber_delta=1.0, depth_mode=DEPTH_UNIFORM,
+                  fields=("e", "sq_norm", "inlier")) -> Residuals:
+        """Per-match residuals at (rot, tran), formed on the device exactly as the sweep forms them.  `fields` picks the
+        arrays copied back (any of "e", "sq_norm", "inlier"; empty = the inlier count only).  n - n_inlier equals the
+        sweep's n_outlier at the same arguments."""
+        unknown = set(fields) - {"e", "sq_norm", "inlier"}
+        if unknown:
+            raise ValueError(f"unknown residual fields {sorted(unknown)}")
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        n = self.size
+        e = np.empty((n, 3)) if "e" in fields else None
+        sq = np.empty(n) if "sq_norm" in fields else None
+        inl = np.empty(n, dtype=np.uint8) if "inlier" in fields else None
+        cnt = C.c_size_t(0)
+        cabi.check(self._lib, self._lib.sba_problem_residuals(
+            self._h, depth_mode, _dptr(rot), _dptr(tran), d1, d2, huber_delta,
+            None if e is None else _dptr(e), None if sq is None else _dptr(sq),
+            None if inl is None else inl.ctypes.data_as(C.c_void_p), C.byref(cnt)))
+        return Residuals(e, sq, None if inl is None else inl.view(np.bool_), cnt.value)
+
+    def compact(self, keep) -> np.ndarray:
+        """Keep the matches where `keep` (length = size) is true, in order; the handle then equals a fresh upload of the
+        kept matches.  Returns their original indices (np.int64)."""
+        k = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, dtype=np.uint8)
+        n = self.size
+        if k.shape[0] != n:
+            raise ValueError(f"keep has {k.shape[0]} entries, the problem holds {n} matches")
+        idx = np.empty(n, dtype=np.int64)
+        kept = C.c_size_t(0)
+        cabi.check(self._lib, self._lib.sba_problem_compact(self._h, k.ctypes.data_as(C.c_void_p), C.byref(kept),
+                                                            idx.ctypes.data_as(C.c_void_p)))
+        return idx[:kept.value].copy()
+
+    def keep_inliers(self, rot, tran, d1=1.0, d2=1.0, huber_delta=1.0, depth_mode=DEPTH_UNIFORM) -> np.ndarray:
+        """Drop the matches in Huber's outlier region at (rot, tran): residuals() then compact().  Returns the original
+        indices of the matches kept."""
+        r = self.residuals(rot, tran, d1, d2, huber_delta, depth_mode, fields=("inlier",))
+        return self.compact(r.inlier)
 
     # -- solve stage --------------------------------------------------------------------------------
     def solve(self, mode, rot, tran, d1=1.0, d2=1.0, depth_mode=DEPTH_UNIFORM, options: cabi.LmOptions | None = None):

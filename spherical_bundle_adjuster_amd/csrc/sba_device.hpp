@@ -220,6 +220,35 @@ hipError_t launch_planes_to_d12(const double* d1, const double* d2, size_t n, do
 hipError_t launch_fold_depths(const void* const coord[6], const double* d1, const double* d2, double* const folded[6],
                               size_t elems, int grid_cap, hipStream_t stream);
 
+// Per-match residuals (sba_select.hip: residual_kernel).  e [elems][3], sq [elems], inlier [elems]: whole vectors of the
+// planes' element type (f64: 2 matches, f32: 4), written only where `outputs` (bit 0 e, bit 1 sq, bit 2 inlier) asks;
+// n_inlier: one zeroed device word that receives the inlier count.  depth as for launch_sweep.
+struct ResidualOut {
+  double* e;
+  double* sq;
+  unsigned char* inlier;
+  unsigned long long* n_inlier;
+};
+hipError_t launch_residuals(int depth, int store, int outputs, const Planes& pl, const SweepParams& prm,
+                            const ResidualOut& out, int grid, hipStream_t stream);
+// Stable compaction of a single problem's planes (sba_select.hip).  keep: ntiles * kCompactTile bytes, zero beyond n.
+// count: tile_count[ntiles]; scan (one block): tile_offset[ntiles] exclusive, total[0] = kept matches; scatter: every kept
+// match i of src[c] to dst[c][tile_offset + rank] (c < 6 coordinate planes of the store's type, 6 and 7 the f64 depth
+// planes when src[6] != null), kept_index (may be null) receives i.
+constexpr int kCompactTile = 2048;   // matches per scan tile: 8 rounds of one 256-thread block
+struct CompactArgs {
+  const unsigned char* keep;
+  size_t n;
+  const unsigned long long* tile_offset;
+  const void* src[8];
+  void* dst[8];
+  long long* kept_index;
+};
+hipError_t launch_compact_count(const unsigned char* keep, size_t ntiles, unsigned int* tile_count, hipStream_t stream);
+hipError_t launch_compact_scan(const unsigned int* tile_count, size_t ntiles, unsigned long long* tile_offset,
+                               unsigned long long* total, hipStream_t stream);
+hipError_t launch_compact_scatter(int store, const CompactArgs& args, size_t ntiles, hipStream_t stream);
+
 // d-only stage (spherical_bundle_adjuster.cpp:1004-1063): one LM iteration of the global bounded problem.
 struct DepthParams {
   double R[9];

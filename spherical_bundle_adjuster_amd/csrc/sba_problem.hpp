@@ -2,6 +2,7 @@
 //   sba_shim.cpp       errors, handle life cycle, uploads, sweeps, eval / solve entry points, side entry points
 //   sba_transport.cpp  multi-GPU transports: RCCL (bound at run time), direct peer exchange, user hook; pack all-reduce
 //   sba_stages.cpp     d-only stage and 8-point initial guess entry points
+//   sba_select.cpp     per-match residuals and compaction of the matches
 // Internal: nothing here is exported from the library.
 #pragma once
 #include <cstdlib>
@@ -35,6 +36,8 @@ struct sba_problem {
   size_t depth_scratch_bytes = 0;
   void* subset_scratch = nullptr;  // reference sampling: [trials][45] moments, then the [trials][m] index lists; kept across calls
   size_t subset_scratch_bytes = 0;
+  void* select_scratch = nullptr;  // per-match residuals: inlier count, then the requested outputs; kept across calls
+  size_t select_scratch_bytes = 0;
   double frame_B[9], frame_J[9];  // factored kernel: host-side frame of the last enqueued sweep
   int last_mode = 0;
 
@@ -179,6 +182,18 @@ class ResidentSession {
   double *a1_ = nullptr, *a2_ = nullptr, *b1_ = nullptr, *b2_ = nullptr, *sc1_ = nullptr, *sc2_ = nullptr;
   unsigned long long pending_cmd_ = 0, pending_pack_ = 0;   // what the next launched kernel waits for / answers with
 };
+
+// sba_shim.cpp -- the plane helpers the other entry points share.
+// ensure_plane: slot k holds at least `bytes` bytes, zeroed (enqueued).  alloc_planes: the zeroed, staggered planes of an
+// upload of n matches (slots 0..7; the handle is not `uploaded` until the caller says so).  ensure_folded: the folded
+// planes brought up to date if the handle sweeps them.  sweep_planes: what a single-problem sweep of `depth_mode` streams
+// and the kernel variant that reads them (sba::kDepthFolded for the folded planes).  check_args: the argument checks of
+// every sweep entry point.
+int ensure_plane(sba_problem* p, int k, size_t bytes);
+int alloc_planes(sba_problem* p, size_t n, bool with_d12, int store);
+int ensure_folded(sba_problem* p);
+int sweep_planes(sba_problem* p, int depth_mode, sba::Planes* pl, int* kernel_depth);
+int check_args(const sba_problem* p, int mode, int depth_mode, const double* rot, const double* tran);
 
 // sba_transport.cpp
 int allreduce_pack(sba_problem* p);                                  // p->pack_dev (24 doubles), then hand-over to the host

@@ -247,6 +247,9 @@ int free_planes(sba_problem* p) {
   return SBA_OK;
 }
 
+}  // namespace
+namespace sba {
+namespace shim {
 // Plane k: at least `bytes` bytes, zeroed.  An existing allocation that is large enough -- and not more than four times too
 // large -- is kept (the usual case: one handle fed image pair after image pair of similar size).
 int ensure_plane(sba_problem* p, int k, size_t bytes) {
@@ -261,6 +264,11 @@ int ensure_plane(sba_problem* p, int k, size_t bytes) {
   return SBA_OK;
 }
 
+}  // namespace shim
+}  // namespace sba
+namespace {
+using sba::shim::ensure_plane;
+
 // The folded planes (slots 8..13) go back to the device.
 int release_folded(sba_problem* p) {
   p->folded_valid = false;
@@ -273,6 +281,9 @@ int release_folded(sba_problem* p) {
   return SBA_OK;
 }
 
+}  // namespace
+namespace sba {
+namespace shim {
 int alloc_planes(sba_problem* p, size_t n, bool with_d12, int store) {
   p->uploaded = false;
   p->folded_valid = false;
@@ -310,19 +321,22 @@ int alloc_planes(sba_problem* p, size_t n, bool with_d12, int store) {
   return SBA_OK;
 }
 
-}  // namespace
-namespace sba {
+}  // namespace shim
 // Referenced weakly: the host translation units are also linked on their own against a mock device (tests/harness), whose
 // stub launchers predate this one.  Without it a handle simply sweeps the raw planes.  The library always defines it.
 hipError_t launch_fold_depths(const void* const coord[6], const double* d1, const double* d2, double* const folded[6],
                               size_t elems, int grid_cap, hipStream_t stream) __attribute__((weak));
 }  // namespace sba
 namespace {
+using sba::shim::alloc_planes;
 
 bool fold_eligible(const sba_problem* p) {
   return p->folding && p->uploaded && p->has_d12 && p->store == SBA_STORE_F64 && !p->fold_failed;
 }
 
+}  // namespace
+namespace sba {
+namespace shim {
 // Bring the folded planes up to date (enqueued on the problem's stream): X1 = d1 x1, X2 = d2 x2 over the whole allocated
 // length, so the zero padding of the raw planes carries over.  Same sizes and stagger as the coordinate planes.  If they
 // cannot be allocated the handle keeps sweeping the raw planes -- the same bits, only slower -- until the next upload.
@@ -370,6 +384,12 @@ int sweep_planes(sba_problem* p, int depth_mode, sba::Planes* pl, int* kernel_de
   return SBA_OK;
 }
 
+}  // namespace shim
+}  // namespace sba
+namespace {
+using sba::shim::ensure_folded;
+using sba::shim::sweep_planes;
+
 // One resident wave of blocks: min(blocks needed, CUs x resident blocks per CU of this kernel).  depth_mode: launch_sweep's
 // depth (sba::kDepthFolded for the folded planes).
 int grid_for(sba_problem* p, int mode, int depth_mode, bool loss, int* grid) {
@@ -397,6 +417,9 @@ int grid_for(sba_problem* p, int mode, int depth_mode, bool loss, int* grid) {
   return SBA_OK;
 }
 
+}  // namespace
+namespace sba {
+namespace shim {
 int check_args(const sba_problem* p, int mode, int depth_mode, const double* rot, const double* tran) {
   if (!p) return fail(SBA_ERR_INVALID_ARG, "null problem handle");
   SBA_REFUSE_POISONED(p);
@@ -412,6 +435,10 @@ int check_args(const sba_problem* p, int mode, int depth_mode, const double* rot
       return fail(SBA_ERR_INVALID_ARG, "non-finite rot/tran");
   return SBA_OK;
 }
+}  // namespace shim
+}  // namespace sba
+namespace {
+using sba::shim::check_args;
 
 void make_params(const sba_problem* p, int depth_mode, const double rot[3], const double tran[3],
                  double d1, double d2, double huber_delta, sba::SweepParams* prm) {
@@ -642,6 +669,7 @@ int sba_problem_destroy(sba_problem* p) {
   if (p->peer_sticky) (void)hipFree(p->peer_sticky);
   if (p->epi_scratch) (void)hipFree(p->epi_scratch);
   if (p->subset_scratch) (void)hipFree(p->subset_scratch);
+  if (p->select_scratch) (void)hipFree(p->select_scratch);
   if (p->depth_scratch) (void)hipFree(p->depth_scratch);
   if (p->pack_host) (void)hipHostFree(p->pack_host);
   if (p->res_rec) (void)hipHostFree(p->res_rec);

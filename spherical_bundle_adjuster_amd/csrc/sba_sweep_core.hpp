@@ -132,22 +132,23 @@ __device__ __forceinline__ double mul_rounded(double a, double b) {
   return a * b;
 }
 
-// Per-match depths follow the reference's order (every cost functor of spherical_bundle_adjuster.cpp: X1 = cam1 d1,
-// X2 = cam2 d2, then R X1): the rounded products X1 = d1 x1 and X2 = d2 x2 first, then v = Rn X1 and e = v + (X2 + t).
-// DEPTH_FOLDED loads X1, X2 as stored by fold_depths_kernel (sba_side.hip) -- the same rounded products -- so both forms
-// give the same bits per match.
-template <int MODE, int DEPTH, int KIND, bool LOSS>
-__device__ __forceinline__ void accumulate(const SweepParams* __restrict__ P, double x, double y,
-                                           double z, double u, double v, double q, double d1, double d2,
-                                           bool valid, double* __restrict__ acc) {
+// The residual of one correspondence, shared by the sweep (accumulate below) and the per-match residual kernel
+// (sba_select.hip), so both form the same bits.  Per-match depths follow the reference's order (every cost functor of
+// spherical_bundle_adjuster.cpp: X1 = cam1 d1, X2 = cam2 d2, then R X1): the rounded products X1 = d1 x1 and X2 = d2 x2
+// first, then v = Rn X1 and e = v + (X2 + t).  DEPTH_FOLDED loads X1, X2 as stored by fold_depths_kernel (sba_side.hip)
+// -- the same rounded products -- so both forms give the same bits per match.  On return x..q hold X1, X2 (per-match
+// depths applied), r = v and e the residual.
+template <int DEPTH>
+__device__ __forceinline__ void residual(const SweepParams* __restrict__ P, double& x, double& y, double& z, double& u,
+                                         double& v, double& q, double d1, double d2, double& r0, double& r1,
+                                         double& r2, double& e0, double& e1, double& e2) {
   if (DEPTH == DEPTH_PER_MATCH) {
     x = mul_rounded(d1, x); y = mul_rounded(d1, y); z = mul_rounded(d1, z);
     u = mul_rounded(d2, u); v = mul_rounded(d2, v); q = mul_rounded(d2, q);
   }
-  const double r0 = P->Rn[0] * x + P->Rn[1] * y + P->Rn[2] * z;
-  const double r1 = P->Rn[3] * x + P->Rn[4] * y + P->Rn[5] * z;
-  const double r2 = P->Rn[6] * x + P->Rn[7] * y + P->Rn[8] * z;
-  double e0, e1, e2;
+  r0 = P->Rn[0] * x + P->Rn[1] * y + P->Rn[2] * z;
+  r1 = P->Rn[3] * x + P->Rn[4] * y + P->Rn[5] * z;
+  r2 = P->Rn[6] * x + P->Rn[7] * y + P->Rn[8] * z;
   if (DEPTH != DEPTH_UNIFORM) {
     e0 = r0 + (u + P->t[0]);
     e1 = r1 + (v + P->t[1]);
@@ -157,7 +158,18 @@ __device__ __forceinline__ void accumulate(const SweepParams* __restrict__ P, do
     e1 = r1 + __builtin_fma(P->d2, v, P->t[1]);
     e2 = r2 + __builtin_fma(P->d2, q, P->t[2]);
   }
-  const double s = e0 * e0 + e1 * e1 + e2 * e2;
+}
+
+// s = e.e, the argument of the Huber loss (also the residual kernel's squared norm and inlier test)
+__device__ __forceinline__ double sq_norm(double e0, double e1, double e2) { return e0 * e0 + e1 * e1 + e2 * e2; }
+
+template <int MODE, int DEPTH, int KIND, bool LOSS>
+__device__ __forceinline__ void accumulate(const SweepParams* __restrict__ P, double x, double y,
+                                           double z, double u, double v, double q, double d1, double d2,
+                                           bool valid, double* __restrict__ acc) {
+  double r0, r1, r2, e0, e1, e2;
+  residual<DEPTH>(P, x, y, z, u, v, q, d1, d2, r0, r1, r2, e0, e1, e2);
+  const double s = sq_norm(e0, e1, e2);
   double w = 1.0, rho = s, is_out = 0.0;
   if (LOSS) huber(s, P->delta, P->delta2, w, rho, is_out);
   if (!valid) { w = 0.0; rho = 0.0; is_out = 0.0; }
