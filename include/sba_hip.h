@@ -485,6 +485,32 @@ int sba_batch_solve_problem(sba_batch* b, int use_initial_guess, int trials, dou
 int sba_batch_solve_depths(sba_batch* b, const double* rot, const double* tran, double lambda, double c,
                            const sba_lm_options* opt, double* d12_out, sba_lm_summary* summaries, int* status);
 
+/* ---- single matches of a batch: residuals, inlier sets, compaction ---- */
+/* Rows r = 0 .. total - 1 with total = offsets[num_pairs] - offsets[0] of the current layout; row r is the caller's row
+ * offsets[0] + r.  rot, tran, d1, d2 as for sba_batch_eval (per pair; NULL depths mean 1.0; ignored with
+ * SBA_DEPTH_PER_MATCH).  Every output may be NULL:
+ *   e_xyz    double[total][3]   each match's residual, formed as the batched sweep forms it
+ *   sq_norm  double[total]      s = e.e
+ *   inlier   uint8[total]       !(s > huber_delta^2); all 1 when huber_delta <= 0; a NaN residual is an inlier
+ *   n_inlier size_t[num_pairs]  inliers per pair: n[g] - n_inlier[g] equals SBA_PACK_NOUT of sba_batch_eval's pack g at the
+ *                               same arguments                                                                           */
+int sba_batch_residuals(sba_batch* b, int depth_mode, const double* rot, const double* tran, const double* d1,
+                        const double* d2, double huber_delta, double* e_xyz, double* sq_norm, unsigned char* inlier,
+                        size_t* n_inlier);
+/* Keep the rows with keep[r] != 0 (host array of total bytes; may be NULL when total is 0), in order; each pair keeps its
+ * own rows and may become empty.  n_kept (size_t[num_pairs], not NULL) receives every pair's kept count, kept_index (may be
+ * NULL; capacity total) the kept row numbers.  Afterwards the handle is what sba_batch_upload of the kept rows (coordinates,
+ * and depths if the batch has them) with the same store and offsets = the exclusive scan of n_kept from 0 would build: same
+ * pairs, layout, blocks per pair and plane contents, so every later call gives the same bits as on such a handle;
+ * sba_batch_set_depths then takes the new row count and d12_out of the solves is indexed by the new rows.  Compacted on the
+ * device, deterministic; the per-pair count is the one synchronous step.  On an error the handle may be left without pairs
+ * (SBA_ERR_NOT_UPLOADED after).                                                                                       */
+int sba_batch_compact(sba_batch* b, const unsigned char* keep, size_t* n_kept, long long* kept_index);
+/* sba_batch_residuals' inlier flags, then sba_batch_compact with them as keep -- the flags never leave the device: only
+ * the per-pair counts come back before the new layout (and the kept row numbers, if asked for).                        */
+int sba_batch_keep_inliers(sba_batch* b, int depth_mode, const double* rot, const double* tran, const double* d1,
+                           const double* d2, double huber_delta, size_t* n_kept, long long* kept_index);
+
 /* ---- callers / data formats either side of the path ------------------------------------- */
 /* pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298).  keypoints: n records of
  * `stride_bytes` bytes whose first two floats are pt.x, pt.y (cv::KeyPoint: stride 28).

@@ -49,6 +49,15 @@ class Residuals(NamedTuple):
     n_inlier: int
 
 
+class BatchResiduals(NamedTuple):
+    """Per-match residuals of a batch (Batch.residuals), rows in the order of Batch.offsets; a field that was not requested
+    is None."""
+    e: np.ndarray | None          # (rows, 3)
+    sq_norm: np.ndarray | None    # (rows,)
+    inlier: np.ndarray | None     # (rows,) bool
+    n_inlier: np.ndarray          # (num_pairs,) int64: inliers per pair
+
+
 def _f64(a, shape=None) -> np.ndarray:
     a = np.ascontiguousarray(a, dtype=np.float64)
     if shape is not None and a.shape != shape:
@@ -398,6 +407,7 @@ class Batch:
         cabi.check(self._lib, self._lib.sba_batch_create(C.byref(self._h), device, C.c_void_p(stream or 0)))
         self.num_pairs = 0
         self._total = 0
+        self._offsets = np.zeros(1, dtype=np.uint64)
 
     def close(self) -> None:
         """As Problem.close(): `destroy_status` != 0 = the batch was poisoned and its device resources were leaked."""
@@ -441,6 +451,7 @@ class Batch:
         cabi.check(self._lib, self._lib.sba_batch_upload(
             self._h, x1.ctypes.data_as(C.c_void_p), x2.ctypes.data_as(C.c_void_p), dp,
             off.ctypes.data_as(C.POINTER(C.c_size_t)), self.num_pairs, store))
+        self._offsets = off.copy()
 
     def set_depths(self, d12) -> None:
         """Re-send only the per-match depths (total, 2), laid out like the d12 of upload(); the coordinates stay resident."""
@@ -448,6 +459,12 @@ class Batch:
         if self.num_pairs and d.shape[0] != self._total:
             raise ValueError("d12 length differs from the uploaded pairs")
         cabi.check(self._lib, self._lib.sba_batch_set_depths(self._h, _dptr(d)))
+
+    @property
+    def offsets(self) -> np.ndarray:
+        """Row offsets (num_pairs + 1,) of the current layout: as uploaded, or the exclusive scan of the kept counts after a
+        compaction.  A copy."""
+        return self._offsets.copy()
 
     @property
     def blocks_per_pair(self) -> int:
@@ -515,6 +532,69 @@ class Batch:
         if rc < 0:
             cabi.check(self._lib, rc)
         return rc == 1
+
+    # -- single matches ---------------------------------------------------------------------------------
+    def _rows(self) -> int:
+        return int(self._offsets[-1]) - int(self._offsets[0])
+
+    def residuals(self, rot, tran, d1=None, d2=None, huber_delta=1.0, depth_mode=DEPTH_UNIFORM,
+                  fields=("e", "sq_norm", "inlier")) -> BatchResiduals:
+        """Every pair's per-match residuals at its own (rot, tran) (B, 3), formed on the device as the batched sweep forms
+        them; rows as in `offsets`.  `fields` picks the arrays copied back (any of "e", "sq_norm", "inlier"; empty = the
+        per-pair inlier counts only).  n[g] - n_inlier[g] equals the pack's n_outlier of eval() at the same arguments."""
+        unknown = set(fields) - {"e", "sq_norm", "inlier"}
+        if unknown:
+            raise ValueError(f"unknown residual fields {sorted(unknown)}")
+        rot, rp = self._pp(rot, 3)
+        tran, tp = self._pp(tran, 3)
+        d1a, d1p = self._pp(d1, 1)
+        d2a, d2p = self._pp(d2, 1)
+        rows = self._rows()
+        e = np.empty((rows, 3)) if "e" in fields else None
+        sq = np.empty(rows) if "sq_norm" in fields else None
+        inl = np.empty(rows, dtype=np.uint8) if "inlier" in fields else None
+        cnt = np.zeros(max(self.num_pairs, 1), dtype=np.uintp)
+        cabi.check(self._lib, self._lib.sba_batch_residuals(
+            self._h, depth_mode, rp, tp, d1p, d2p, huber_delta, None if e is None else _dptr(e),
+            None if sq is None else _dptr(sq), None if inl is None else inl.ctypes.data_as(C.c_void_p),
+            cnt.ctypes.data_as(C.POINTER(C.c_size_t))))
+        return BatchResiduals(e, sq, None if inl is None else inl.view(np.bool_), cnt[:self.num_pairs].astype(np.int64))
+
+    def _compacted(self, idx, n_kept):
+        off = np.zeros(self.num_pairs + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(n_kept[:self.num_pairs], dtype=np.uint64)
+        self._offsets = off
+        self._total = int(off[-1])
+        return idx[:self._total].copy(), off.copy()
+
+    def compact(self, keep):
+        """Keep the rows where `keep` (one entry per row of `offsets`) is true, in order; every pair keeps its own rows.  The
+        handle then equals a fresh upload of the kept rows with offsets from 0.  Returns (kept row numbers (np.int64),
+        the new offsets)."""
+        k = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, dtype=np.uint8)
+        rows = self._rows()
+        if k.shape[0] != rows:
+            raise ValueError(f"keep has {k.shape[0]} entries, the batch holds {rows} rows")
+        idx = np.empty(max(rows, 1), dtype=np.int64)
+        nk = np.zeros(max(self.num_pairs, 1), dtype=np.uintp)
+        cabi.check(self._lib, self._lib.sba_batch_compact(self._h, k.ctypes.data_as(C.c_void_p),
+                                                          nk.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                                          idx.ctypes.data_as(C.c_void_p)))
+        return self._compacted(idx, nk)
+
+    def keep_inliers(self, rot, tran, d1=None, d2=None, huber_delta=1.0, depth_mode=DEPTH_UNIFORM):
+        """Drop every pair's matches in Huber's outlier region at its (rot, tran): residuals() then compact(), with the
+        inlier mask kept on the device.  Returns what compact() returns."""
+        rot, rp = self._pp(rot, 3)
+        tran, tp = self._pp(tran, 3)
+        d1a, d1p = self._pp(d1, 1)
+        d2a, d2p = self._pp(d2, 1)
+        idx = np.empty(max(self._rows(), 1), dtype=np.int64)
+        nk = np.zeros(max(self.num_pairs, 1), dtype=np.uintp)
+        cabi.check(self._lib, self._lib.sba_batch_keep_inliers(self._h, depth_mode, rp, tp, d1p, d2p, huber_delta,
+                                                               nk.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                                               idx.ctypes.data_as(C.c_void_p)))
+        return self._compacted(idx, nk)
 
     def solve(self, mode, rot, tran, d1=None, d2=None, depth_mode=DEPTH_UNIFORM, options: cabi.LmOptions | None = None):
         """Per-pair LM in lock-step.  Returns (rot (B,3), tran (B,3), [SolveSummary], status (B,))."""

@@ -13,83 +13,15 @@
 #include <thread>
 #include <vector>
 
+#include "sba_batch.hpp"
 #include "sba_depth_solver.hpp"
 #include "sba_epipolar.hpp"
 #include "sba_internal.hpp"
 #include "sba_lm.hpp"
 #include "sba_rotation.hpp"
 
-struct sba_batch {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  int poisoned = 0;            // a device wait timed out or the device faulted (sba_internal.hpp): the handle is refused
-                               // from then on -- its ticket word and sequence numbers are out of step -- destroy leaks
-  int num_cus = 0;
-  int kind = SBA_KERNEL_FACTORED;
-
-  int num_pairs = 0;
-  int store = SBA_STORE_F64;
-  bool has_d12 = false;
-  bool uploaded = false;
-  std::vector<size_t> n;            // matches per pair
-  std::vector<size_t> first_vec;    // first 16-byte vector of the pair inside the planes
-  size_t tile_stride = 256;         // vectors between consecutive 256-vector tiles of a pair (256 = contiguous pairs; sba_device.hpp: PairDesc)
-  size_t total_vecs = 0;
-  void* coord[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  double* dplane[2] = {nullptr, nullptr};
-  void* plane_base[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // hipMalloc'ed blocks
-  size_t plane_stagger = 4352;   // plane k starts k * 4352 B into its allocation (as sba_problem: equal element indices of
-                                 // the 8 streams then differ in their low address bits); SBA_PLANE_STAGGER overrides
-  sba::PairDesc* desc_dev = nullptr;
-  sba::SweepParams* params_dev = nullptr;    // built on the device by batch_prepare_kernel
-  sba::BatchState* state_host = nullptr;     // pinned + mapped: what the host hands over per pair and step (80 B)
-  sba::BatchState* state_host_dev = nullptr; // device-visible address of state_host
-  double* frames_dev = nullptr;              // [pair][18]: (B, J) of the pair's rotation, for the moment conversion
-  double* partials = nullptr;
-  int bpp = 1;                                // blocks per pair
-  double* packs_dev = nullptr;
-  double* packs_host = nullptr;               // pinned + mapped: 24 doubles per pair, then the sequence word
-  double* packs_host_dev = nullptr;           // device-visible address of packs_host
-  unsigned long long seq = 0;                 // launches published so far
-  bool publish = true;                        // SBA_PUBLISH=0: D2H copy + stream synchronise instead
-  sba::BatchLmIo* lm_io_host = nullptr;       // pinned + mapped: per-pair start point in, result + summary out (batch_lm_kernel)
-  sba::BatchLmIo* lm_io_host_dev = nullptr;   // device-visible address of lm_io_host
-  unsigned int* lm_ticket = nullptr;          // device: blocks of batch_lm_kernel that have delivered their record
-  std::vector<size_t> offsets;                // row offset of every pair in the caller's concatenated arrays (num_pairs + 1)
-  size_t plane_elems = 0;                     // elements per plane
-  // batched d-only stage (allocated on first use, kept while the batch lives)
-  double* depth_work = nullptr;               // 4 planes: candidate depths (2), Jacobi scaling (2)
-  sba::BatchDepthConst* depth_const_dev = nullptr;
-  sba::BatchDepthPass* depth_pass_host = nullptr;     // pinned + mapped
-  sba::BatchDepthPass* depth_pass_host_dev = nullptr;
-  double* depth_out_host = nullptr;           // pinned + mapped: [num_pairs][16] results, then the sequence word
-  double* depth_out_host_dev = nullptr;
-  unsigned long long depth_seq = 0;
-  // batched initial guess (allocated on first use): the 64 x 45 group moments of every pair
-  double* epi_groups_dev = nullptr;
-  double* epi_groups_host = nullptr;          // pinned
-  sba::BatchGuessOut* guess_out_dev = nullptr;
-  sba::BatchGuessOut* guess_out_host = nullptr;   // pinned
-  // device-resident solves with dynamic shares (allocated on first use)
-  sba::BatchDynCtl* dyn_ctl = nullptr;
-  unsigned int* dyn_active = nullptr;        // [2][num_pairs]
-  int* dyn_done = nullptr;                   // [num_pairs]
-  void* dyn_state = nullptr;                 // per-pair solver state
-  double* dyn_partials = nullptr;            // share rows of one launch
-  size_t dyn_partial_rows = 0;
-  unsigned long long* dyn_host = nullptr;    // pinned + mapped: [0] pairs still active, [1] sequence word
-  unsigned long long* dyn_host_dev = nullptr;
-  unsigned long long dyn_seq = 0;
-  sba::BatchDepthPass* dyn_depth_req = nullptr;   // [num_pairs]: the next pass of every pair of the d-only stage
-  unsigned char* dyn_finish = nullptr;            // [num_pairs]: what batch_depth_finish_kernel has left to do
-  // upload: row offsets on the device (relative to the first row), two pinned staging buffers, their DMA-done events
-  unsigned long long* offsets_dev = nullptr;
-  void* upload_pinned[2] = {nullptr, nullptr};
-  hipEvent_t upload_ev[2] = {nullptr, nullptr};
-};
-
-namespace {
+namespace sba {
+namespace batch {
 
 int free_batch_data(sba_batch* b) {
   for (auto& pb : b->plane_base) { if (pb) SBA_TRY_HIP(hipFree(pb)); pb = nullptr; }
@@ -124,6 +56,8 @@ int free_batch_data(sba_batch* b) {
   b->desc_dev = nullptr; b->params_dev = nullptr; b->state_host = nullptr; b->state_host_dev = nullptr;
   b->frames_dev = nullptr; b->partials = nullptr;
   b->packs_dev = nullptr; b->packs_host = nullptr; b->packs_host_dev = nullptr;
+  if (b->select_scratch) SBA_TRY_HIP(hipFree(b->select_scratch));
+  b->select_scratch = nullptr; b->select_scratch_bytes = 0;
   b->uploaded = false; b->num_pairs = 0; b->n.clear(); b->first_vec.clear();
   return SBA_OK;
 }
@@ -141,6 +75,123 @@ int check_batch_args(const sba_batch* b, int mode, int depth_mode, const double*
   return SBA_OK;
 }
 
+void write_state(sba_batch* b, const double* rot, const double* tran, const double* d1, const double* d2,
+                 const unsigned char* active) {
+  for (int g = 0; g < b->num_pairs; ++g) {
+    sba::BatchState& st = b->state_host[g];
+    for (int a = 0; a < 3; ++a) { st.rot[a] = rot[3 * g + a]; st.tran[a] = tran[3 * g + a]; }
+    st.d1 = d1 ? d1[g] : 1.0;
+    st.d2 = d2 ? d2[g] : 1.0;
+    st.n = (!active || active[g]) ? b->n[g] : 0;
+    st.pad_ = 0;
+  }
+}
+
+int layout_pairs(sba_batch* b, const size_t* offsets, int num_pairs, int store, bool has_d12) {
+  b->num_pairs = num_pairs;
+  b->store = store;
+  b->has_d12 = has_d12;
+  // every pair starts on a whole vector; vectors are sized for the widest lane group (4 elements) so that the
+  // same offsets serve f64 (2 per vector) and f32 (4 per vector) planes, plus one spare vector for the tail load
+  const size_t ppt = static_cast<size_t>(sba::points_per_lane(store));
+  b->n.resize(num_pairs);
+  b->first_vec.resize(num_pairs);
+  size_t vec = 0, max_n = 0;
+  std::vector<sba::PairDesc> desc(num_pairs);
+  for (int g = 0; g < num_pairs; ++g) {
+    b->n[g] = offsets[g + 1] - offsets[g];
+    b->first_vec[g] = vec;
+    desc[g] = sba::PairDesc{vec, b->n[g], sba::kPairTile, 0ull};
+    vec += (b->n[g] + ppt - 1) / ppt + 1;
+    max_n = std::max(max_n, b->n[g]);
+  }
+  // Layout.  Contiguous pairs (above) make every block of a one-block-per-pair sweep its own sequential stream per plane:
+  // num_pairs x 8 streams.  INTERLEAVED (tile t of every pair side by side, 4 KiB tiles) the blocks, which advance in step,
+  // read one contiguous window of every plane like the single-problem grid-stride sweep does (8 streams): 3-4 % more of the
+  // HBM bandwidth (tools/stream_probe.hip: stride vs chunk; measured on the C5 step: DESIGN.md section 3.5).  It pads
+  // every pair to the longest one's tile count, so it is used when that wastes at most a quarter (SBA_BATCH_INTERLEAVE = 0 /
+  // 1 forces either).
+  const size_t tiles = ((max_n + ppt - 1) / ppt + 1 + sba::kPairTile - 1) / sba::kPairTile;      // of the longest pair, spare vector included
+  const size_t inter_vecs = tiles * static_cast<size_t>(num_pairs) * sba::kPairTile;
+  bool interleave = num_pairs >= 2 && inter_vecs <= vec + vec / 4;
+  if (const char* env = std::getenv("SBA_BATCH_INTERLEAVE")) interleave = num_pairs >= 1 && env[0] != '0';
+  b->tile_stride = sba::kPairTile;
+  if (interleave && max_n > 0) {
+    b->tile_stride = sba::kPairTile * static_cast<size_t>(num_pairs);
+    for (int g = 0; g < num_pairs; ++g) {
+      b->first_vec[g] = static_cast<size_t>(g) * sba::kPairTile;
+      desc[g] = sba::PairDesc{b->first_vec[g], b->n[g], b->tile_stride, 0ull};
+    }
+    vec = inter_vecs;
+  }
+  b->total_vecs = vec + 1;
+  const size_t elems = b->total_vecs * ppt, esz = store == SBA_STORE_F64 ? 8 : 4;
+  b->plane_elems = elems;
+  // An empty batch may come without an offsets array (the argument check admits NULL for num_pairs == 0): keep {0}.
+  if (num_pairs == 0) b->offsets.assign(1, 0);
+  else b->offsets.assign(offsets, offsets + num_pairs + 1);
+  for (int k = 0; k < 6; ++k) {
+    const size_t lead = b->plane_stagger * static_cast<size_t>(k);
+    SBA_TRY_HIP(hipMalloc(&b->plane_base[k], lead + elems * esz));
+    SBA_TRY_HIP(hipMemsetAsync(b->plane_base[k], 0, lead + elems * esz, b->stream));
+    b->coord[k] = static_cast<char*>(b->plane_base[k]) + lead;
+  }
+  if (has_d12)
+    for (int k = 0; k < 2; ++k) {
+      const size_t lead = b->plane_stagger * static_cast<size_t>(6 + k);
+      SBA_TRY_HIP(hipMalloc(&b->plane_base[6 + k], lead + elems * 8));
+      SBA_TRY_HIP(hipMemsetAsync(b->plane_base[6 + k], 0, lead + elems * 8, b->stream));
+      b->dplane[k] = reinterpret_cast<double*>(static_cast<char*>(b->plane_base[6 + k]) + lead);
+    }
+  if (num_pairs == 0) return SBA_OK;
+
+  // Blocks per pair: with at least one pair per CU, one block per pair (measured best at 256 pairs x 50k matches:
+  // 198 / 206 / 205 / 213 us per step for 1 / 2 / 3 / 4 blocks per pair); with fewer pairs, spread each pair over
+  // enough blocks to put two blocks on every CU like the single-problem sweep -- never more than a pair can use.
+  const size_t need = (((max_n + ppt - 1) / ppt) + sba::kBlock - 1) / sba::kBlock;
+  const size_t share = num_pairs >= b->num_cus ? 1 : static_cast<size_t>(2 * b->num_cus) / num_pairs;
+  b->bpp = static_cast<int>(std::max<size_t>(1, std::min(std::max<size_t>(need, 1), share)));
+  if (const char* env = std::getenv("SBA_BATCH_BPP")) { const int v = std::atoi(env); if (v >= 1 && v <= 1024) b->bpp = v; }
+
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->desc_dev), sizeof(sba::PairDesc) * num_pairs));
+  SBA_TRY_HIP(hipMemcpy(b->desc_dev, desc.data(), sizeof(sba::PairDesc) * num_pairs, hipMemcpyHostToDevice));
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->params_dev), sizeof(sba::SweepParams) * num_pairs));
+  SBA_TRY_HIP(hipMemset(b->params_dev, 0, sizeof(sba::SweepParams) * num_pairs));   // n = 0 until a prepare kernel has run
+  SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->state_host), sizeof(sba::BatchState) * num_pairs,
+                            hipHostMallocMapped | hipHostMallocCoherent));
+  std::memset(b->state_host, 0, sizeof(sba::BatchState) * num_pairs);
+  SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->state_host_dev), b->state_host, 0));
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->frames_dev), sizeof(double) * 18 * num_pairs));
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->partials), sizeof(double) * sba::kRow * num_pairs * b->bpp));
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->packs_dev), sizeof(double) * 24 * num_pairs));
+  SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->packs_host), sizeof(double) * (24 * num_pairs + 8),
+                            hipHostMallocMapped | hipHostMallocCoherent));
+  std::memset(b->packs_host, 0, sizeof(double) * (24 * num_pairs + 8));
+  SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->packs_host_dev), b->packs_host, 0));
+  SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->lm_io_host), sizeof(sba::BatchLmIo) * num_pairs,
+                            hipHostMallocMapped | hipHostMallocCoherent));
+  std::memset(b->lm_io_host, 0, sizeof(sba::BatchLmIo) * num_pairs);
+  SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->lm_io_host_dev), b->lm_io_host, 0));
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->lm_ticket), 64));
+  SBA_TRY_HIP(hipMemset(b->lm_ticket, 0, 64));
+  b->seq = 0;
+
+  {
+    std::vector<unsigned long long> off64(num_pairs + 1);
+    for (int g = 0; g <= num_pairs; ++g) off64[g] = offsets[g] - offsets[0];
+    SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->offsets_dev), sizeof(unsigned long long) * off64.size()));
+    SBA_TRY_HIP(hipMemcpy(b->offsets_dev, off64.data(), sizeof(unsigned long long) * off64.size(), hipMemcpyHostToDevice));
+  }
+  return SBA_OK;
+}
+}  // namespace batch
+}  // namespace sba
+
+using sba::batch::check_batch_args;
+using sba::batch::free_batch_data;
+
+namespace {
+
 // One batched step: pair g is evaluated at (rot[g], tran[g]) unless active[g] == 0.  The host writes 80 bytes per pair
 // into mapped pinned memory; batch_prepare_kernel builds every pair's sweep state from it ON THE DEVICE, the sweep runs,
 // and the finalize kernel folds the rows, maps the factored kernel's moments to the SBA_PACK_* layout (also on the
@@ -155,14 +206,7 @@ int batch_launch(sba_batch* b, int mode, int depth_mode, const double* rot, cons
                  bool allow_fused = true) {
   const int B = b->num_pairs;
   const auto t_prep = std::chrono::steady_clock::now();
-  for (int g = 0; g < B; ++g) {
-    sba::BatchState& st = b->state_host[g];
-    for (int a = 0; a < 3; ++a) { st.rot[a] = rot[3 * g + a]; st.tran[a] = tran[3 * g + a]; }
-    st.d1 = d1 ? d1[g] : 1.0;
-    st.d2 = d2 ? d2[g] : 1.0;
-    st.n = (!active || active[g]) ? b->n[g] : 0;
-    st.pad_ = 0;
-  }
+  sba::batch::write_state(b, rot, tran, d1, d2, active);
   if (prepare_ms)
     *prepare_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_prep).count();
   sba::Planes pl;
@@ -415,100 +459,9 @@ int sba_batch_upload(sba_batch* b, const double* left_xyz, const double* right_x
     return batch_transfer(b, left_xyz, right_xyz, d12, 7u);
   int rc = free_batch_data(b);
   if (rc) return rc;
-  b->num_pairs = num_pairs;
-  b->store = store;
-  b->has_d12 = d12 != nullptr;
-  // every pair starts on a whole vector; vectors are sized for the widest lane group (4 elements) so that the
-  // same offsets serve f64 (2 per vector) and f32 (4 per vector) planes, plus one spare vector for the tail load
-  const size_t ppt = static_cast<size_t>(sba::points_per_lane(store));
-  b->n.resize(num_pairs);
-  b->first_vec.resize(num_pairs);
-  size_t vec = 0, max_n = 0;
-  std::vector<sba::PairDesc> desc(num_pairs);
-  for (int g = 0; g < num_pairs; ++g) {
-    b->n[g] = offsets[g + 1] - offsets[g];
-    b->first_vec[g] = vec;
-    desc[g] = sba::PairDesc{vec, b->n[g], sba::kPairTile, 0ull};
-    vec += (b->n[g] + ppt - 1) / ppt + 1;
-    max_n = std::max(max_n, b->n[g]);
-  }
-  // Layout.  Contiguous pairs (above) make every block of a one-block-per-pair sweep its own sequential stream per plane:
-  // num_pairs x 8 streams.  INTERLEAVED (tile t of every pair side by side, 4 KiB tiles) the blocks, which advance in step,
-  // read one contiguous window of every plane like the single-problem grid-stride sweep does (8 streams): 3-4 % more of the
-  // HBM bandwidth (tools/stream_probe.hip: stride vs chunk; measured on the C5 step: DESIGN.md section 3.5).  It pads
-  // every pair to the longest one's tile count, so it is used when that wastes at most a quarter (SBA_BATCH_INTERLEAVE = 0 /
-  // 1 forces either).
-  const size_t tiles = ((max_n + ppt - 1) / ppt + 1 + sba::kPairTile - 1) / sba::kPairTile;      // of the longest pair, spare vector included
-  const size_t inter_vecs = tiles * static_cast<size_t>(num_pairs) * sba::kPairTile;
-  bool interleave = num_pairs >= 2 && inter_vecs <= vec + vec / 4;
-  if (const char* env = std::getenv("SBA_BATCH_INTERLEAVE")) interleave = num_pairs >= 1 && env[0] != '0';
-  b->tile_stride = sba::kPairTile;
-  if (interleave && max_n > 0) {
-    b->tile_stride = sba::kPairTile * static_cast<size_t>(num_pairs);
-    for (int g = 0; g < num_pairs; ++g) {
-      b->first_vec[g] = static_cast<size_t>(g) * sba::kPairTile;
-      desc[g] = sba::PairDesc{b->first_vec[g], b->n[g], b->tile_stride, 0ull};
-    }
-    vec = inter_vecs;
-  }
-  b->total_vecs = vec + 1;
-  const size_t elems = b->total_vecs * ppt, esz = store == SBA_STORE_F64 ? 8 : 4;
-  b->plane_elems = elems;
-  // An empty batch may come without an offsets array (the argument check admits NULL for num_pairs == 0): keep {0}.
-  if (num_pairs == 0) b->offsets.assign(1, 0);
-  else b->offsets.assign(offsets, offsets + num_pairs + 1);
-  for (int k = 0; k < 6; ++k) {
-    const size_t lead = b->plane_stagger * static_cast<size_t>(k);
-    SBA_TRY_HIP(hipMalloc(&b->plane_base[k], lead + elems * esz));
-    SBA_TRY_HIP(hipMemsetAsync(b->plane_base[k], 0, lead + elems * esz, b->stream));
-    b->coord[k] = static_cast<char*>(b->plane_base[k]) + lead;
-  }
-  if (d12)
-    for (int k = 0; k < 2; ++k) {
-      const size_t lead = b->plane_stagger * static_cast<size_t>(6 + k);
-      SBA_TRY_HIP(hipMalloc(&b->plane_base[6 + k], lead + elems * 8));
-      SBA_TRY_HIP(hipMemsetAsync(b->plane_base[6 + k], 0, lead + elems * 8, b->stream));
-      b->dplane[k] = reinterpret_cast<double*>(static_cast<char*>(b->plane_base[6 + k]) + lead);
-    }
+  rc = sba::batch::layout_pairs(b, offsets, num_pairs, store, d12 != nullptr);
+  if (rc) return rc;
   if (num_pairs == 0) { b->uploaded = true; return SBA_OK; }
-
-  // Blocks per pair: with at least one pair per CU, one block per pair (measured best at 256 pairs x 50k matches:
-  // 198 / 206 / 205 / 213 us per step for 1 / 2 / 3 / 4 blocks per pair); with fewer pairs, spread each pair over
-  // enough blocks to put two blocks on every CU like the single-problem sweep -- never more than a pair can use.
-  const size_t need = (((max_n + ppt - 1) / ppt) + sba::kBlock - 1) / sba::kBlock;
-  const size_t share = num_pairs >= b->num_cus ? 1 : static_cast<size_t>(2 * b->num_cus) / num_pairs;
-  b->bpp = static_cast<int>(std::max<size_t>(1, std::min(std::max<size_t>(need, 1), share)));
-  if (const char* env = std::getenv("SBA_BATCH_BPP")) { const int v = std::atoi(env); if (v >= 1 && v <= 1024) b->bpp = v; }
-
-  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->desc_dev), sizeof(sba::PairDesc) * num_pairs));
-  SBA_TRY_HIP(hipMemcpy(b->desc_dev, desc.data(), sizeof(sba::PairDesc) * num_pairs, hipMemcpyHostToDevice));
-  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->params_dev), sizeof(sba::SweepParams) * num_pairs));
-  SBA_TRY_HIP(hipMemset(b->params_dev, 0, sizeof(sba::SweepParams) * num_pairs));   // n = 0 until a prepare kernel has run
-  SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->state_host), sizeof(sba::BatchState) * num_pairs,
-                            hipHostMallocMapped | hipHostMallocCoherent));
-  std::memset(b->state_host, 0, sizeof(sba::BatchState) * num_pairs);
-  SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->state_host_dev), b->state_host, 0));
-  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->frames_dev), sizeof(double) * 18 * num_pairs));
-  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->partials), sizeof(double) * sba::kRow * num_pairs * b->bpp));
-  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->packs_dev), sizeof(double) * 24 * num_pairs));
-  SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->packs_host), sizeof(double) * (24 * num_pairs + 8),
-                            hipHostMallocMapped | hipHostMallocCoherent));
-  std::memset(b->packs_host, 0, sizeof(double) * (24 * num_pairs + 8));
-  SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->packs_host_dev), b->packs_host, 0));
-  SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->lm_io_host), sizeof(sba::BatchLmIo) * num_pairs,
-                            hipHostMallocMapped | hipHostMallocCoherent));
-  std::memset(b->lm_io_host, 0, sizeof(sba::BatchLmIo) * num_pairs);
-  SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->lm_io_host_dev), b->lm_io_host, 0));
-  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->lm_ticket), 64));
-  SBA_TRY_HIP(hipMemset(b->lm_ticket, 0, 64));
-  b->seq = 0;
-
-  {
-    std::vector<unsigned long long> off64(num_pairs + 1);
-    for (int g = 0; g <= num_pairs; ++g) off64[g] = offsets[g] - offsets[0];
-    SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->offsets_dev), sizeof(unsigned long long) * off64.size()));
-    SBA_TRY_HIP(hipMemcpy(b->offsets_dev, off64.data(), sizeof(unsigned long long) * off64.size(), hipMemcpyHostToDevice));
-  }
   rc = batch_transfer(b, left_xyz, right_xyz, d12, 7u);
   if (rc) return rc;
   b->uploaded = true;

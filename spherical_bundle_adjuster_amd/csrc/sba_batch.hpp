@@ -1,0 +1,97 @@
+// The batch handle (sba_batch.cpp) and what the translation units that work on it share (sba_batch_select.cpp).
+#pragma once
+#include <vector>
+
+#include "sba_internal.hpp"
+
+struct sba_batch {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  int poisoned = 0;            // a device wait timed out or the device faulted (sba_internal.hpp): the handle is refused
+                               // from then on -- its ticket word and sequence numbers are out of step -- destroy leaks
+  int num_cus = 0;
+  int kind = SBA_KERNEL_FACTORED;
+
+  int num_pairs = 0;
+  int store = SBA_STORE_F64;
+  bool has_d12 = false;
+  bool uploaded = false;
+  std::vector<size_t> n;            // matches per pair
+  std::vector<size_t> first_vec;    // first 16-byte vector of the pair inside the planes
+  size_t tile_stride = 256;         // vectors between consecutive 256-vector tiles of a pair (256 = contiguous pairs; sba_device.hpp: PairDesc)
+  size_t total_vecs = 0;
+  void* coord[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double* dplane[2] = {nullptr, nullptr};
+  void* plane_base[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // hipMalloc'ed blocks
+  size_t plane_stagger = 4352;   // plane k starts k * 4352 B into its allocation (as sba_problem: equal element indices of
+                                 // the 8 streams then differ in their low address bits); SBA_PLANE_STAGGER overrides
+  sba::PairDesc* desc_dev = nullptr;
+  sba::SweepParams* params_dev = nullptr;    // built on the device by batch_prepare_kernel
+  sba::BatchState* state_host = nullptr;     // pinned + mapped: what the host hands over per pair and step (80 B)
+  sba::BatchState* state_host_dev = nullptr; // device-visible address of state_host
+  double* frames_dev = nullptr;              // [pair][18]: (B, J) of the pair's rotation, for the moment conversion
+  double* partials = nullptr;
+  int bpp = 1;                                // blocks per pair
+  double* packs_dev = nullptr;
+  double* packs_host = nullptr;               // pinned + mapped: 24 doubles per pair, then the sequence word
+  double* packs_host_dev = nullptr;           // device-visible address of packs_host
+  unsigned long long seq = 0;                 // launches published so far
+  bool publish = true;                        // SBA_PUBLISH=0: D2H copy + stream synchronise instead
+  sba::BatchLmIo* lm_io_host = nullptr;       // pinned + mapped: per-pair start point in, result + summary out (batch_lm_kernel)
+  sba::BatchLmIo* lm_io_host_dev = nullptr;   // device-visible address of lm_io_host
+  unsigned int* lm_ticket = nullptr;          // device: blocks of batch_lm_kernel that have delivered their record
+  std::vector<size_t> offsets;                // row offset of every pair in the caller's concatenated arrays (num_pairs + 1)
+  size_t plane_elems = 0;                     // elements per plane
+  // batched d-only stage (allocated on first use, kept while the batch lives)
+  double* depth_work = nullptr;               // 4 planes: candidate depths (2), Jacobi scaling (2)
+  sba::BatchDepthConst* depth_const_dev = nullptr;
+  sba::BatchDepthPass* depth_pass_host = nullptr;     // pinned + mapped
+  sba::BatchDepthPass* depth_pass_host_dev = nullptr;
+  double* depth_out_host = nullptr;           // pinned + mapped: [num_pairs][16] results, then the sequence word
+  double* depth_out_host_dev = nullptr;
+  unsigned long long depth_seq = 0;
+  // batched initial guess (allocated on first use): the 64 x 45 group moments of every pair
+  double* epi_groups_dev = nullptr;
+  double* epi_groups_host = nullptr;          // pinned
+  sba::BatchGuessOut* guess_out_dev = nullptr;
+  sba::BatchGuessOut* guess_out_host = nullptr;   // pinned
+  // device-resident solves with dynamic shares (allocated on first use)
+  sba::BatchDynCtl* dyn_ctl = nullptr;
+  unsigned int* dyn_active = nullptr;        // [2][num_pairs]
+  int* dyn_done = nullptr;                   // [num_pairs]
+  void* dyn_state = nullptr;                 // per-pair solver state
+  double* dyn_partials = nullptr;            // share rows of one launch
+  size_t dyn_partial_rows = 0;
+  unsigned long long* dyn_host = nullptr;    // pinned + mapped: [0] pairs still active, [1] sequence word
+  unsigned long long* dyn_host_dev = nullptr;
+  unsigned long long dyn_seq = 0;
+  sba::BatchDepthPass* dyn_depth_req = nullptr;   // [num_pairs]: the next pass of every pair of the d-only stage
+  unsigned char* dyn_finish = nullptr;            // [num_pairs]: what batch_depth_finish_kernel has left to do
+  // upload: row offsets on the device (relative to the first row), two pinned staging buffers, their DMA-done events
+  unsigned long long* offsets_dev = nullptr;
+  void* upload_pinned[2] = {nullptr, nullptr};
+  hipEvent_t upload_ev[2] = {nullptr, nullptr};
+  // per-match residuals (sba_batch_residuals, allocated on first use): the per-pair inlier counts, then the outputs
+  void* select_scratch = nullptr;
+  size_t select_scratch_bytes = 0;
+};
+
+namespace sba {
+namespace batch {
+
+// Releases every device and mapped buffer of the batch's pairs (not the stream, the upload staging buffers or the kernel kind).
+int free_batch_data(sba_batch* b);
+int check_batch_args(const sba_batch* b, int mode, int depth_mode, const double* rot, const double* tran);
+// The 80-byte per-pair state of one evaluation at (rot, tran, d1, d2) (NULL depths: 1.0) into mapped host memory; a pair with
+// active[g] == 0 takes part with n = 0.
+void write_state(sba_batch* b, const double* rot, const double* tran, const double* d1, const double* d2,
+                 const unsigned char* active);
+// Layout and allocation from the row offsets of the pairs (num_pairs + 1, non-decreasing, kept as given): per-pair n, where
+// every pair starts (contiguous or interleaved: SBA_BATCH_INTERLEAVE), the zeroed planes, blocks per pair (SBA_BATCH_BPP),
+// the descriptors and the row offsets (relative to offsets[0]) on the device, and the per-pair mapped buffers.  The handle
+// must hold no pair data (free_batch_data).  An upload and a compaction both lay out a batch through here.
+int layout_pairs(sba_batch* b, const size_t* offsets, int num_pairs, int store, bool has_d12);
+
+}  // namespace batch
+}  // namespace sba

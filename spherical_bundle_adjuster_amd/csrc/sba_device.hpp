@@ -126,6 +126,31 @@ constexpr unsigned long long kPairTile = 256;   // vectors per tile = threads pe
 SBA_HD inline unsigned long long pair_vector(const PairDesc& d, unsigned long long p) {
   return d.first_vec + (p / kPairTile) * d.tile_stride + (p % kPairTile);
 }
+// tile_elems == 0: element i -> first + i.  Otherwise (interleaved batch layout, PairDesc): tiles of tile_elems consecutive
+// elements sit tile_stride_elems apart.
+SBA_HD inline size_t tiled_index(size_t first, size_t i, size_t tile_elems, size_t tile_stride_elems) {
+  return tile_elems == 0 ? first + i : first + (i / tile_elems) * tile_stride_elems + i % tile_elems;
+}
+// The pair of row `row` of a batch's concatenated rows (pair g = rows offsets[g] .. offsets[g + 1]), by bisection of the
+// offsets (a few KB, L2-resident); empty pairs repeat an offset: the last one wins.
+SBA_HD inline int batch_pair_of(size_t row, const unsigned long long* __restrict__ offsets, int num_pairs) {
+  int lo = 0, hi = num_pairs;                 // offsets[lo] <= row < offsets[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offsets[mid] <= row) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// Element index of element `i` of pair `d` inside the planes (ppt elements per 16-byte vector).
+SBA_HD inline size_t pair_element(const PairDesc& d, size_t i, size_t ppt) {
+  return tiled_index(d.first_vec * ppt, i, kPairTile * ppt, d.tile_stride * ppt);
+}
+// Row -> element of the pair's tiles.
+SBA_HD inline size_t batch_row_index(size_t row, const unsigned long long* __restrict__ offsets, int num_pairs,
+                                     const PairDesc* __restrict__ desc, size_t ppt) {
+  const int g = batch_pair_of(row, offsets, num_pairs);
+  return pair_element(desc[g], row - offsets[g], ppt);
+}
 // What the host hands over per pair and step (mapped pinned host memory, 80 B per pair): the point to evaluate at and
 // the number of matches that take part (0 = pair already converged).
 struct BatchState {
@@ -248,6 +273,34 @@ hipError_t launch_compact_count(const unsigned char* keep, size_t ntiles, unsign
 hipError_t launch_compact_scan(const unsigned int* tile_count, size_t ntiles, unsigned long long* tile_offset,
                                unsigned long long* total, hipStream_t stream);
 hipError_t launch_compact_scatter(int store, const CompactArgs& args, size_t ntiles, hipStream_t stream);
+
+// The same two for a batch (sba_select.hip).  Residuals: pair g (blocks g * bpp ... g * bpp + bpp - 1, strided over its
+// vectors as the batched sweep) builds its SweepParams on the device from state[g] (fill_sweep_params, as the step kernels
+// do) and writes the outputs `outputs` asks for to rows offsets[g] + i (e [rows][3], sq [rows], inlier [rows]: element by
+// element); n_inlier: num_pairs zeroed device words.
+hipError_t launch_batch_residuals(int depth, int store, int outputs, const Planes& pl, const PairDesc* desc,
+                                  const unsigned long long* offsets, const BatchState* state, double huber_delta,
+                                  int num_pairs, int bpp, const ResidualOut& out, hipStream_t stream);
+// Compaction: keep as for a single problem, over the concatenated rows (tile counts and scan: launch_compact_count / _scan);
+// pair_kept[g] = kept rows of pair g (one wave per pair, from the tile offsets); the scatter moves every kept row from its
+// element of the old layout (old_offsets, old_desc) to its element of the new one.  Offsets relative to the first row.
+struct BatchCompactArgs {
+  const unsigned char* keep;
+  size_t rows;
+  const unsigned long long* tile_offset;
+  const unsigned long long* old_offsets;
+  const PairDesc* old_desc;
+  const unsigned long long* new_offsets;
+  const PairDesc* new_desc;
+  int num_pairs;
+  const void* src[8];
+  void* dst[8];
+  long long* kept_index;
+};
+hipError_t launch_batch_pair_kept(const unsigned char* keep, const unsigned long long* tile_offset, size_t ntiles,
+                                  const unsigned long long* total, const unsigned long long* offsets, int num_pairs,
+                                  unsigned long long* pair_kept, hipStream_t stream);
+hipError_t launch_batch_compact_scatter(int store, const BatchCompactArgs& args, size_t ntiles, hipStream_t stream);
 
 // d-only stage (spherical_bundle_adjuster.cpp:1004-1063): one LM iteration of the global bounded problem.
 struct DepthParams {

@@ -8,11 +8,6 @@ namespace sba {
 namespace {
 
 // ---- layout conversion at upload time (once per problem, not per LM iteration) ---------------
-// tile_elems == 0: element i -> first + i.  Otherwise (interleaved batch layout, sba_device.hpp: PairDesc): tiles of
-// tile_elems consecutive elements sit tile_stride_elems apart.
-__device__ __forceinline__ size_t tiled_index(size_t first, size_t i, size_t tile_elems, size_t tile_stride_elems) {
-  return tile_elems == 0 ? first + i : first + (i / tile_elems) * tile_stride_elems + i % tile_elems;
-}
 template <typename ST>
 __global__ void aos_to_planes_kernel(const double* __restrict__ aos, size_t n, size_t first,
                                      ST* __restrict__ px, ST* __restrict__ py, ST* __restrict__ pz, size_t tile_elems,
@@ -34,18 +29,8 @@ __global__ void d12_to_planes_kernel(const double* __restrict__ d12, size_t n, s
   d2[o] = d.y;
 }
 // The same re-layout for a whole batch in one launch: rows [first_row, first_row + m) of the caller's CONCATENATED arrays
-// (pair g = rows offsets[g] .. offsets[g + 1]) sit in `stage`; every row finds its pair by bisection of the offsets (a few KB,
-// L2-resident) and goes to its place in the pair's tiles (PairDesc).  One launch per staged chunk instead of one per pair.
-__device__ __forceinline__ size_t batch_row_index(size_t row, const unsigned long long* __restrict__ offsets, int num_pairs,
-                                                  const PairDesc* __restrict__ desc, size_t ppt) {
-  int lo = 0, hi = num_pairs;                 // offsets[lo] <= row < offsets[hi]; empty pairs repeat an offset: the last one wins
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (offsets[mid] <= row) lo = mid; else hi = mid;
-  }
-  const PairDesc d = desc[lo];
-  return tiled_index(d.first_vec * ppt, row - offsets[lo], kPairTile * ppt, d.tile_stride * ppt);
-}
+// (pair g = rows offsets[g] .. offsets[g + 1]) sit in `stage`; every row goes to its place in the pair's tiles
+// (batch_row_index, sba_device.hpp).  One launch per staged chunk instead of one per pair.
 template <typename ST>
 __global__ void batch_aos_to_planes_kernel(const double* __restrict__ aos, size_t m, size_t first_row,
                                            const unsigned long long* __restrict__ offsets, int num_pairs,
