@@ -17,6 +17,18 @@ RT_TOL_F64 = 1e-9        # recovered rot (rad) / tran, f64 planes
 RT_TOL_F32 = 1e-5
 
 
+def make_pairs(sizes, seed0=900, rt=True):
+    """A batch of seeded synthetic pairs (full_rt, or rotation_only with rt=False): the per-pair Correspondences, the row
+    offsets (B + 1,) and the concatenated x1, x2 and d12 arrays in the layout Batch.upload takes."""
+    from spherical_bundle_adjuster_amd import synthetic
+    cs = [(synthetic.full_rt if rt else synthetic.rotation_only)(n, seed=seed0 + i) for i, n in enumerate(sizes)]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
+    x1 = np.concatenate([c.x1 for c in cs]) if sum(sizes) else np.zeros((0, 3))
+    x2 = np.concatenate([c.x2 for c in cs]) if sum(sizes) else np.zeros((0, 3))
+    d12 = np.concatenate([c.d12 for c in cs]) if rt and sum(sizes) else (np.zeros((0, 2)) if rt else None)
+    return cs, off, x1, x2, d12
+
+
 def declared_functions():
     txt = HEADER.read_text()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)

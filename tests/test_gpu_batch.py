@@ -7,19 +7,11 @@ import numpy as np
 import pytest
 
 from helpers import REL_TOL_F64, RT_TOL_F64, pack_from_eval
+from helpers import make_pairs as _make_pairs
 from spherical_bundle_adjuster_amd import _cabi as cabi
 from spherical_bundle_adjuster_amd import api, synthetic
 
 pytestmark = pytest.mark.gpu
-
-
-def _make_pairs(sizes, seed0=900, rt=True):
-    cs = [(synthetic.full_rt if rt else synthetic.rotation_only)(n, seed=seed0 + i) for i, n in enumerate(sizes)]
-    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)
-    x1 = np.concatenate([c.x1 for c in cs]) if sum(sizes) else np.zeros((0, 3))
-    x2 = np.concatenate([c.x2 for c in cs]) if sum(sizes) else np.zeros((0, 3))
-    d12 = np.concatenate([c.d12 for c in cs]) if rt and sum(sizes) else (np.zeros((0, 2)) if rt else None)
-    return cs, off, x1, x2, d12
 
 
 @pytest.mark.parametrize("kind", [api.KERNEL_FACTORED, api.KERNEL_EXPLICIT], ids=["factored", "explicit"])
