@@ -26,6 +26,8 @@
  *       -> sba_rotate_keypoints(), sba_crop_rotated_image(), sba_cube2equi_keypoints()
  *   - one run of main/main.cpp per image pair
  *       -> sba_batch_*()                   (many pairs per launch, one LM per pair)
+ *   - feature_matcher::match_two_image (feature_matcher.cpp:42-59: FLANN 2-NN + ratio test)
+ *       -> sba_match_descriptors(), sba_batch_match_descriptors(), sba_*_upload_matches()
  *
  * Conventions
  *   - every function returns an int status: 0 = SBA_OK, negative = error; the text of the
@@ -565,6 +567,55 @@ long sba_map_table_host_decided(int device, int kind, int param, int im_height, 
  * them are staged (the rest gather from global memory), LDS bytes per frame.  0, or -1 if the table is not built.      */
 int sba_map_table_tiles(int device, int kind, int param, int im_height, int im_width, int* tiles, int* staged_tiles,
                         int* lds_bytes_per_frame);
+
+/* ---- descriptor matching (feature_matcher::match_two_image, feature_matcher.cpp:42-59) -------------------------- */
+/* Exact L2 2-nearest neighbours of every query row among the train rows, then the reference's ratio test
+ * d0 < ratio * d1 (0.3 there), in float on the reported distances.  Descriptors: f32 rows of `dim` values
+ * (1 <= dim <= 256; SURF 64, extended SURF 128), `row_stride_bytes` apart (a multiple of 4, >= 4 * dim: a cv::Mat
+ * passes as Mat::ptr<float>() and Mat::step).  Query = the left image (queryIdx), train = the right (trainIdx).
+ *   nn_index / nn_dist  [n_query][2] (NULL = not wanted): the two neighbours, nearest first, and their Euclidean
+ *                       distances (DMatch::distance); -1 and +inf where there is none.
+ *   n_matched           the accepted queries; match_query / match_train / match_dist (capacity n_query each, NULL =
+ *                       not wanted): the accepted (queryIdx, trainIdx, distance) in ascending query order -- the
+ *                       reference's good_matches.
+ * Ranking is lexicographic on (score, train index) -- the lowest index wins a tie; the two winners are rescored as
+ * sum_k (q_k - t_k)^2 in f32 and reordered by (distance, index).  The result of a query is a pure function of the query row,
+ * the train rows, dim and ratio.  A query row with a non-finite component matches nothing; a train row with one is never
+ * chosen; with fewer than two train rows nothing matches (the reference reads knn_matches[i][1] then: undefined behaviour).
+ * Deviation: OpenCV's FlannBasedMatcher (randomised kd-trees) is approximate; this is the exact answer it approximates.
+ * The count is the one synchronous step.                                                                            */
+int sba_match_descriptors(int device, const float* query, size_t n_query, const float* train, size_t n_train, int dim,
+                          size_t row_stride_bytes, float ratio, int* nn_index, float* nn_dist, size_t* n_matched,
+                          int* match_query, int* match_train, float* match_dist);
+/* The same on device pointers and a HIP stream (NULL = the default stream); every output array is a device array.      */
+int sba_match_descriptors_device(int device, void* stream, const float* query_dev, size_t n_query, const float* train_dev,
+                                 size_t n_train, int dim, size_t row_stride_bytes, float ratio, int* nn_index_dev,
+                                 float* nn_dist_dev, size_t* n_matched, int* match_query_dev, int* match_train_dev,
+                                 float* match_dist_dev);
+/* Many pairs in one launch: pair g matches query rows query_offsets[g] .. [g + 1] against train rows train_offsets[g] ..
+ * [g + 1] (non-decreasing; empty pairs allowed).  Indices are local to the pair; nn_* are indexed by query row -
+ * query_offsets[0]; n_matched[num_pairs]; the match_* arrays hold pair 0's matches, then pair 1's, ...              */
+int sba_batch_match_descriptors(int device, const float* query, const size_t* query_offsets, const float* train,
+                                const size_t* train_offsets, int num_pairs, int dim, size_t row_stride_bytes, float ratio,
+                                int* nn_index, float* nn_dist, size_t* n_matched, int* match_query, int* match_train,
+                                float* match_dist);
+/* Match, then upload the matched key-points: afterwards the handle equals sba_problem_upload_keypoints() of the records
+ * left_keypoints[match_left[i]], right_keypoints[match_right[i]] (i < *n_matched), with d12 = (d, d) per match when
+ * init_depth points at a depth d (the reference's init_d fill, spherical_bundle_adjuster.cpp:325-326).  Key-point records
+ * as sba_problem_upload_keypoints; descriptors as sba_match_descriptors, one row per key-point.  The gather runs on the
+ * device: only the count and the indices (match_left / match_right, capacity n_left, NULL = not wanted) come back. */
+int sba_problem_upload_matches(sba_problem* p, const void* left_keypoints, size_t n_left, const void* right_keypoints,
+                               size_t n_right, size_t stride_bytes, int im_width, int im_height, const float* left_desc,
+                               const float* right_desc, int dim, size_t row_stride_bytes, float ratio, const double* init_depth,
+                               int store, size_t* n_matched, int* match_left, int* match_right);
+/* The same for every pair of a batch (offsets as sba_batch_match_descriptors, for key-points and descriptors alike):
+ * afterwards the batch equals sba_batch_upload() of sba_keypoints_to_sphere() of the matched records with offsets = the
+ * exclusive scan of n_matched[num_pairs], and d12 = (init_depth[g], init_depth[g]) for the matches of pair g when
+ * init_depth (double[num_pairs]) is given.  match_left / match_right: pair-local indices, concatenated in pair order.  */
+int sba_batch_upload_matches(sba_batch* b, const void* left_keypoints, const size_t* left_offsets, const void* right_keypoints,
+                             const size_t* right_offsets, int num_pairs, size_t stride_bytes, int im_width, int im_height,
+                             const float* left_desc, const float* right_desc, int dim, size_t row_stride_bytes, float ratio,
+                             const double* init_depth, int store, size_t* n_matched, int* match_left, int* match_right);
 
 #ifdef __cplusplus
 }

@@ -174,6 +174,16 @@ SIGNATURES = {
                                       C.POINTER(C.c_int)]),
     "sba_equi2cube": (C.c_int, [C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "sba_equi2cube_device": (C.c_int, [C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "sba_match_descriptors": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_float, _vp, _vp,
+                                        C.POINTER(C.c_size_t), _vp, _vp, _vp]),
+    "sba_match_descriptors_device": (C.c_int, [C.c_int, _vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_float,
+                                               _vp, _vp, C.POINTER(C.c_size_t), _vp, _vp, _vp]),
+    "sba_batch_match_descriptors": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_size_t, C.c_float, _vp, _vp,
+                                              _vp, _vp, _vp, _vp]),
+    "sba_problem_upload_matches": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _vp, _vp,
+                                             C.c_int, C.c_size_t, C.c_float, _dp, C.c_int, C.POINTER(C.c_size_t), _vp, _vp]),
+    "sba_batch_upload_matches": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_size_t, C.c_int, C.c_int, _vp, _vp, C.c_int,
+                                           C.c_size_t, C.c_float, _dp, C.c_int, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -69,6 +69,61 @@ def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+class Matches(NamedTuple):
+    """Result of match_descriptors: exact L2 2-NN of every query row and the reference's ratio test."""
+    nn_index: np.ndarray      # (n_query, 2) int32: nearest, second nearest train row; -1 = none
+    nn_distance: np.ndarray   # (n_query, 2) float32: their Euclidean distances (DMatch::distance); +inf = none
+    query_idx: np.ndarray     # (n_matched,) int32: accepted queries, ascending (queryIdx)
+    train_idx: np.ndarray     # (n_matched,) int32: their nearest train row (trainIdx)
+    distance: np.ndarray      # (n_matched,) float32
+
+
+class BatchMatches(NamedTuple):
+    """Result of batch_match_descriptors; indices are local to the pair, pair g's matches are rows
+    match_offsets[g] .. match_offsets[g + 1] of query_idx / train_idx / distance."""
+    nn_index: np.ndarray      # (total queries, 2) int32
+    nn_distance: np.ndarray   # (total queries, 2) float32
+    n_matched: np.ndarray     # (num_pairs,) int64
+    match_offsets: np.ndarray  # (num_pairs + 1,) int64: exclusive scan of n_matched
+    query_idx: np.ndarray
+    train_idx: np.ndarray
+    distance: np.ndarray
+
+
+def _descriptors(*arrays):
+    """f32 (n, dim) descriptor arrays -> (arrays, row stride in bytes).  Rows may be padded (a view of a wider array, like a
+    cv::Mat with a larger step) as long as every array has the same row stride; otherwise they are made contiguous."""
+    out = []
+    for a in arrays:
+        a = np.asarray(a)
+        if a.ndim != 2:
+            raise ValueError("descriptors must be 2-D (n, dim)")
+        if a.dtype != np.float32 or a.strides[1] != 4 or a.strides[0] % 4 or a.strides[0] < 4 * a.shape[1]:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+        out.append(a)
+    dims = {a.shape[1] for a in out}
+    if len(dims) != 1:
+        raise ValueError("descriptor dimensions differ")
+    dim = dims.pop()
+    strides = {a.strides[0] for a in out if a.shape[0] > 1}
+    if len(strides) > 1:
+        out = [np.ascontiguousarray(a) for a in out]
+        strides = {4 * dim}
+    stride = strides.pop() if strides else 4 * dim
+    return out, dim, max(stride, 4 * dim)
+
+
+def _vptr(a: np.ndarray):
+    return C.c_void_p(a.ctypes.data) if a.size else None
+
+
+def _offsets(o, name):
+    off = np.ascontiguousarray(o, dtype=np.uint64)
+    if off.ndim != 1 or off.size < 1:
+        raise ValueError(f"{name} offsets must be 1-D with num_pairs + 1 entries")
+    return off
+
+
 def device_count() -> int:
     lib = cabi.load_library()
     n = C.c_int(0)
@@ -176,6 +231,27 @@ class Problem:
         cabi.check(self._lib, self._lib.sba_problem_upload_keypoints(
             self._h, kl.ctypes.data_as(C.c_void_p), kr.ctypes.data_as(C.c_void_p), n, stride, im_width, im_height, dp,
             store))
+
+    def upload_matches(self, left_kp: np.ndarray, right_kp: np.ndarray, left_desc, right_desc, im_width: int, im_height: int,
+                       ratio: float = 0.3, init_depth: float | None = None, store: int = STORE_F64):
+        """Match the descriptors of both images on the device (match_descriptors: left = query, right = train), then upload
+        the matched key-point records as upload_keypoints would, with d12 = (init_depth, init_depth) per match if given.
+        Key-point records and descriptor rows are one per key-point.  Returns (match_left, match_right): int32 indices."""
+        kl, kr = np.ascontiguousarray(left_kp), np.ascontiguousarray(right_kp)
+        if kl.ndim != 2 or kr.ndim != 2 or kl.dtype != kr.dtype or kl.shape[1] != kr.shape[1]:
+            raise ValueError("left/right key-point records differ in layout")
+        (dl, dr), dim, dstride = _descriptors(left_desc, right_desc)
+        if dl.shape[0] != kl.shape[0] or dr.shape[0] != kr.shape[0]:
+            raise ValueError("one descriptor row per key-point")
+        stride = kl.strides[0] if kl.shape[0] > 0 else (kr.strides[0] if kr.shape[0] > 0 else 28)
+        ml = np.zeros(max(kl.shape[0], 1), dtype=np.int32)
+        mr = np.zeros(max(kl.shape[0], 1), dtype=np.int32)
+        d = None if init_depth is None else (C.c_double * 1)(float(init_depth))
+        n = C.c_size_t()
+        cabi.check(self._lib, self._lib.sba_problem_upload_matches(
+            self._h, _vptr(kl), kl.shape[0], _vptr(kr), kr.shape[0], stride, im_width, im_height, _vptr(dl), _vptr(dr), dim,
+            dstride, ratio, d, store, C.byref(n), ml.ctypes.data_as(C.c_void_p), mr.ctypes.data_as(C.c_void_p)))
+        return ml[:n.value].copy(), mr[:n.value].copy()
 
     def upload_device(self, left_ptr: int, right_ptr: int, d12_ptr: int | None, n: int,
                       store: int = STORE_F64) -> None:
@@ -453,6 +529,46 @@ class Batch:
             off.ctypes.data_as(C.POINTER(C.c_size_t)), self.num_pairs, store))
         self._offsets = off.copy()
 
+    def upload_matches(self, left_kp: np.ndarray, left_offsets, right_kp: np.ndarray, right_offsets, left_desc, right_desc,
+                       im_width: int, im_height: int, ratio: float = 0.3, init_depth=None, store: int = STORE_F64):
+        """Match every pair's descriptors on the device (batch_match_descriptors), then upload the matched key-points of all
+        pairs as upload() of their sphere points would, with offsets = the exclusive scan of the per-pair counts and
+        d12 = (init_depth[g], init_depth[g]) per match of pair g if init_depth (num_pairs,) or a scalar is given.  Offsets
+        index key-point records and descriptor rows alike.  Returns (match_left, match_right, n_matched): pair-local int32
+        indices concatenated in pair order, and the per-pair counts."""
+        kl, kr = np.ascontiguousarray(left_kp), np.ascontiguousarray(right_kp)
+        if kl.ndim != 2 or kr.ndim != 2 or kl.dtype != kr.dtype or kl.shape[1] != kr.shape[1]:
+            raise ValueError("left/right key-point records differ in layout")
+        lo, ro = _offsets(left_offsets, "left"), _offsets(right_offsets, "right")
+        if lo.size != ro.size:
+            raise ValueError("left/right offsets differ in length")
+        B = lo.size - 1
+        (dl, dr), dim, dstride = _descriptors(left_desc, right_desc)
+        if dl.shape[0] != kl.shape[0] or dr.shape[0] != kr.shape[0]:
+            raise ValueError("one descriptor row per key-point")
+        if int(lo[-1]) > kl.shape[0] or int(ro[-1]) > kr.shape[0]:
+            raise ValueError("offsets run past the arrays")
+        stride = kl.strides[0] if kl.shape[0] > 0 else (kr.strides[0] if kr.shape[0] > 0 else 28)
+        dp = None
+        if init_depth is not None:
+            dd = np.ascontiguousarray(np.broadcast_to(np.asarray(init_depth, dtype=np.float64), (B,)))
+            dp = _dptr(dd)
+        nl = max(int(lo[-1] - lo[0]) if B else 0, 1)
+        ml, mr = np.zeros(nl, dtype=np.int32), np.zeros(nl, dtype=np.int32)
+        cnt = np.zeros(max(B, 1), dtype=np.uint64)
+        cabi.check(self._lib, self._lib.sba_batch_upload_matches(
+            self._h, _vptr(kl), lo.ctypes.data_as(C.c_void_p), _vptr(kr), ro.ctypes.data_as(C.c_void_p), B, stride, im_width,
+            im_height, _vptr(dl), _vptr(dr), dim, dstride, ratio, dp, store, cnt.ctypes.data_as(C.c_void_p),
+            ml.ctypes.data_as(C.c_void_p), mr.ctypes.data_as(C.c_void_p)))
+        n = cnt[:B].astype(np.int64)
+        off = np.zeros(B + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(n)
+        self.num_pairs = B
+        self._total = int(off[-1])
+        self._offsets = off
+        m = int(off[-1])
+        return ml[:m].copy(), mr[:m].copy(), n
+
     def set_depths(self, d12) -> None:
         """Re-send only the per-match depths (total, 2), laid out like the d12 of upload(); the coordinates stay resident."""
         d = _f64(d12).reshape(-1, 2)
@@ -720,6 +836,53 @@ def comm_unique_id() -> bytes:
     buf = C.create_string_buffer(cabi.COMM_ID_BYTES)
     cabi.check(lib, lib.sba_comm_unique_id(buf))
     return buf.raw
+
+def match_descriptors(query, train, ratio: float = 0.3, device: int = 0) -> Matches:
+    """feature_matcher::match_two_image on the device: exact L2 2-NN of every query row (n_query, dim) among the train rows
+    (n_train, dim) (f32; 1 <= dim <= 256), then the ratio test d0 < ratio * d1 (reference: 0.3).  The accepted matches come
+    in ascending query order, like the reference's good_matches."""
+    lib = cabi.load_library()
+    (q, t), dim, stride = _descriptors(query, train)
+    nq = q.shape[0]
+    nn_i, nn_d = np.zeros((max(nq, 1), 2), dtype=np.int32), np.zeros((max(nq, 1), 2), dtype=np.float32)
+    mq, mt, md = (np.zeros(max(nq, 1), dtype=np.int32), np.zeros(max(nq, 1), dtype=np.int32),
+                  np.zeros(max(nq, 1), dtype=np.float32))
+    n = C.c_size_t()
+    cabi.check(lib, lib.sba_match_descriptors(device, _vptr(q), nq, _vptr(t), t.shape[0], dim, stride, ratio,
+                                              nn_i.ctypes.data_as(C.c_void_p), nn_d.ctypes.data_as(C.c_void_p), C.byref(n),
+                                              mq.ctypes.data_as(C.c_void_p), mt.ctypes.data_as(C.c_void_p),
+                                              md.ctypes.data_as(C.c_void_p)))
+    m = n.value
+    return Matches(nn_i[:nq], nn_d[:nq], mq[:m].copy(), mt[:m].copy(), md[:m].copy())
+
+
+def batch_match_descriptors(query, query_offsets, train, train_offsets, ratio: float = 0.3, device: int = 0) -> BatchMatches:
+    """match_descriptors for many pairs in one launch: pair g = query rows query_offsets[g] .. [g + 1] against train rows
+    train_offsets[g] .. [g + 1].  nn_* are indexed by query row - query_offsets[0]."""
+    lib = cabi.load_library()
+    (q, t), dim, stride = _descriptors(query, train)
+    qo, to = _offsets(query_offsets, "query"), _offsets(train_offsets, "train")
+    if qo.size != to.size:
+        raise ValueError("query/train offsets differ in length")
+    B = qo.size - 1
+    if B and (int(qo[-1]) > q.shape[0] or int(to[-1]) > t.shape[0]):
+        raise ValueError("offsets run past the arrays")
+    nq = int(qo[-1] - qo[0]) if B else 0
+    nn_i, nn_d = np.zeros((max(nq, 1), 2), dtype=np.int32), np.zeros((max(nq, 1), 2), dtype=np.float32)
+    mq, mt, md = (np.zeros(max(nq, 1), dtype=np.int32), np.zeros(max(nq, 1), dtype=np.int32),
+                  np.zeros(max(nq, 1), dtype=np.float32))
+    cnt = np.zeros(max(B, 1), dtype=np.uint64)
+    cabi.check(lib, lib.sba_batch_match_descriptors(device, _vptr(q), qo.ctypes.data_as(C.c_void_p), _vptr(t),
+                                                    to.ctypes.data_as(C.c_void_p), B, dim, stride, ratio,
+                                                    nn_i.ctypes.data_as(C.c_void_p), nn_d.ctypes.data_as(C.c_void_p),
+                                                    cnt.ctypes.data_as(C.c_void_p), mq.ctypes.data_as(C.c_void_p),
+                                                    mt.ctypes.data_as(C.c_void_p), md.ctypes.data_as(C.c_void_p)))
+    n = cnt[:B].astype(np.int64)
+    off = np.zeros(B + 1, dtype=np.int64)
+    off[1:] = np.cumsum(n)
+    m = int(off[-1])
+    return BatchMatches(nn_i[:nq], nn_d[:nq], n, off, mq[:m].copy(), mt[:m].copy(), md[:m].copy())
+
 
 
 def keypoints_to_sphere(keypoints: np.ndarray, im_width: int, im_height: int, device: int = 0) -> np.ndarray:

@@ -1,9 +1,12 @@
 // Command-line driver with the reference's argument contract (main/main.cpp:8-27):
 //   sba_main <L> <R> <exp roll> <exp pitch> <exp yaw> <exp Tx> <exp Ty> <exp Tz> <exp d>
 // With OpenCV (SBA_WITH_OPENCV) <L>/<R> are ERP images and a matcher must be linked in by the
-// integrator.  Without OpenCV -- this image -- <L>/<R> are files of matched
-// cv::KeyPoint records (28 bytes each, same count, match i = record i), preceded by a 16-byte
-// header {int32 count, int32 im_width, int32 im_height, int32 reserved}.
+// integrator.  Without OpenCV <L>/<R> are files of cv::KeyPoint records (28 bytes
+// each) preceded by a 16-byte header {int32 count, int32 im_width, int32 im_height, int32 dim}:
+//   dim == 0  the records are matched already (same count, match i = record i);
+//   dim > 0   count x dim f32 descriptors (row-major) follow the records; the two files may hold
+//             different counts and are matched first (feature_matcher::match_two_image: exact
+//             2-NN on the device, ratio test 0.3), both files with the same dim.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -14,14 +17,17 @@
 #include "spherical_bundle_adjuster.hpp"
 
 namespace {
-bool read_keypoints(const char* path, std::vector<cv::KeyPoint>* out, int* w, int* h) {
+bool read_keypoints(const char* path, std::vector<cv::KeyPoint>* out, std::vector<float>* desc, int* w, int* h, int* dim) {
   std::ifstream f(path, std::ios::binary);
   int32_t hdr[4];
-  if (!f.read(reinterpret_cast<char*>(hdr), sizeof(hdr)) || hdr[0] < 0) return false;
+  if (!f.read(reinterpret_cast<char*>(hdr), sizeof(hdr)) || hdr[0] < 0 || hdr[3] < 0) return false;
   out->resize(static_cast<size_t>(hdr[0]));
   *w = hdr[1];
   *h = hdr[2];
-  return hdr[0] == 0 || static_cast<bool>(f.read(reinterpret_cast<char*>(out->data()), sizeof(cv::KeyPoint) * out->size()));
+  *dim = hdr[3];
+  if (hdr[0] > 0 && !f.read(reinterpret_cast<char*>(out->data()), sizeof(cv::KeyPoint) * out->size())) return false;
+  desc->resize(out->size() * static_cast<size_t>(hdr[3]));
+  return desc->empty() || static_cast<bool>(f.read(reinterpret_cast<char*>(desc->data()), sizeof(float) * desc->size()));
 }
 }  // namespace
 
@@ -37,13 +43,16 @@ int main(int argc, char** argv) {
   // SBA_INITIAL_GUESS=0: start from the expected values on the command line instead of the 8-point consensus
   if (const char* env = std::getenv("SBA_INITIAL_GUESS")) sph_ba.set_initial_guess(env[0] != '0');
   std::vector<cv::KeyPoint> left_key, right_key;
-  int w = 0, h = 0, w2 = 0, h2 = 0;
-  if (!read_keypoints(argv[1], &left_key, &w, &h) || !read_keypoints(argv[2], &right_key, &w2, &h2) ||
-      left_key.size() != right_key.size() || w != w2 || h != h2) {
-    std::cerr << "cannot read matched key-point files" << std::endl;
+  std::vector<float> left_desc, right_desc;
+  int w = 0, h = 0, w2 = 0, h2 = 0, dim = 0, dim2 = 0;
+  if (!read_keypoints(argv[1], &left_key, &left_desc, &w, &h, &dim) ||
+      !read_keypoints(argv[2], &right_key, &right_desc, &w2, &h2, &dim2) || dim != dim2 ||
+      (dim == 0 && left_key.size() != right_key.size()) || w != w2 || h != h2) {
+    std::cerr << "cannot read key-point files" << std::endl;
     return 1;
   }
-  const int rc = sph_ba.do_bundle_adjustment_from_matches(left_key, right_key, static_cast<int>(left_key.size()), w, h);
+  const int rc = dim > 0 ? sph_ba.do_bundle_adjustment_from_features(left_key, right_key, left_desc, right_desc, dim, w, h)
+                         : sph_ba.do_bundle_adjustment_from_matches(left_key, right_key, static_cast<int>(left_key.size()), w, h);
   if (rc != SBA_OK) {
     std::cerr << "error " << rc << ": " << sba_last_error() << std::endl;
     return 2;

@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "sba_device.hpp"
+#include "sba_match.hpp"
 
 namespace sba {
 namespace {
@@ -96,6 +97,43 @@ __global__ void keypoints_to_planes_kernel(const uint8_t* __restrict__ kp_left, 
   const double s1 = sin(col1), s2 = sin(col2);
   x1x[i] = static_cast<ST>(s1 * cos(lon1)); x1y[i] = static_cast<ST>(s1 * sin(lon1)); x1z[i] = static_cast<ST>(cos(col1));
   x2x[i] = static_cast<ST>(s2 * cos(lon2)); x2y[i] = static_cast<ST>(s2 * sin(lon2)); x2z[i] = static_cast<ST>(cos(col2));
+}
+
+// The two maps above with an index indirection: record i is the one at absolute row rows[i] (the key-point gather of a
+// descriptor match, sba_match.cpp).  The same expressions, compiled under the same flags, so the planes / points carry the
+// bits of the direct maps applied to the gathered records.
+template <typename ST>
+__global__ void keypoints_to_planes_gather_kernel(const uint8_t* __restrict__ kp_left, const uint8_t* __restrict__ kp_right,
+                                                  const unsigned long long* __restrict__ rows_left,
+                                                  const unsigned long long* __restrict__ rows_right, size_t n,
+                                                  size_t stride_bytes, double im_w, double im_h, ST* __restrict__ x1x,
+                                                  ST* __restrict__ x1y, ST* __restrict__ x1z, ST* __restrict__ x2x,
+                                                  ST* __restrict__ x2y, ST* __restrict__ x2z) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double kPi = 3.14159265358979323846;
+  const float* l = reinterpret_cast<const float*>(kp_left + rows_left[i] * stride_bytes);
+  const float* r = reinterpret_cast<const float*>(kp_right + rows_right[i] * stride_bytes);
+  const double lon1 = 2 * kPi * (static_cast<double>(l[0]) / im_w), col1 = kPi * (static_cast<double>(l[1]) / im_h);
+  const double lon2 = 2 * kPi * (static_cast<double>(r[0]) / im_w), col2 = kPi * (static_cast<double>(r[1]) / im_h);
+  const double s1 = sin(col1), s2 = sin(col2);
+  x1x[i] = static_cast<ST>(s1 * cos(lon1)); x1y[i] = static_cast<ST>(s1 * sin(lon1)); x1z[i] = static_cast<ST>(cos(col1));
+  x2x[i] = static_cast<ST>(s2 * cos(lon2)); x2y[i] = static_cast<ST>(s2 * sin(lon2)); x2z[i] = static_cast<ST>(cos(col2));
+}
+__global__ void keypoints_to_sphere_gather_kernel(const uint8_t* __restrict__ kp, const unsigned long long* __restrict__ rows,
+                                                  size_t n, size_t stride_bytes, double im_w, double im_h,
+                                                  double* __restrict__ out_xyz) {
+  const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* rec = reinterpret_cast<const float*>(kp + rows[i] * stride_bytes);
+  const double px = static_cast<double>(rec[0]), py = static_cast<double>(rec[1]);
+  const double kPi = 3.14159265358979323846;
+  const double lon = 2 * kPi * (px / im_w);
+  const double colat = kPi * (py / im_h);
+  const double sc = sin(colat), cc = cos(colat);
+  out_xyz[3 * i + 0] = sc * cos(lon);
+  out_xyz[3 * i + 1] = sc * sin(lon);
+  out_xyz[3 * i + 2] = cc;
 }
 
 // Per-match depths folded into the coordinates: X1 = d1 x1, X2 = d2 x2 (the rounded products the per-match sweep forms,
@@ -211,6 +249,33 @@ hipError_t launch_keypoints_to_planes(const uint8_t* kp_left, const uint8_t* kp_
                        stride_bytes, im_w, im_h, static_cast<float*>(planes[0]), static_cast<float*>(planes[1]),
                        static_cast<float*>(planes[2]), static_cast<float*>(planes[3]), static_cast<float*>(planes[4]),
                        static_cast<float*>(planes[5]));
+  return hipGetLastError();
+}
+
+hipError_t launch_keypoints_to_planes_gather(const uint8_t* kp_left, const uint8_t* kp_right, const unsigned long long* rows_left,
+                                             const unsigned long long* rows_right, size_t n, size_t stride_bytes, double im_w,
+                                             double im_h, void* const planes[6], int store, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const unsigned grid = static_cast<unsigned>((n + 255) / 256);
+  if (store == 0)
+    hipLaunchKernelGGL((keypoints_to_planes_gather_kernel<double>), dim3(grid), dim3(256), 0, stream, kp_left, kp_right, rows_left,
+                       rows_right, n, stride_bytes, im_w, im_h, static_cast<double*>(planes[0]), static_cast<double*>(planes[1]),
+                       static_cast<double*>(planes[2]), static_cast<double*>(planes[3]), static_cast<double*>(planes[4]),
+                       static_cast<double*>(planes[5]));
+  else
+    hipLaunchKernelGGL((keypoints_to_planes_gather_kernel<float>), dim3(grid), dim3(256), 0, stream, kp_left, kp_right, rows_left,
+                       rows_right, n, stride_bytes, im_w, im_h, static_cast<float*>(planes[0]), static_cast<float*>(planes[1]),
+                       static_cast<float*>(planes[2]), static_cast<float*>(planes[3]), static_cast<float*>(planes[4]),
+                       static_cast<float*>(planes[5]));
+  return hipGetLastError();
+}
+
+hipError_t launch_keypoints_to_sphere_gather(const uint8_t* kp, const unsigned long long* rows, size_t n, size_t stride_bytes,
+                                             double im_w, double im_h, double* out_xyz, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  const unsigned grid = static_cast<unsigned>((n + 255) / 256);
+  hipLaunchKernelGGL(keypoints_to_sphere_gather_kernel, dim3(grid), dim3(256), 0, stream, kp, rows, n, stride_bytes, im_w, im_h,
+                     out_xyz);
   return hipGetLastError();
 }
 

@@ -50,6 +50,29 @@ void spherical_bundle_adjuster::do_bundle_adjustment(const cv::Mat& im_left, con
   if (rc != SBA_OK) std::cerr << "spherical_bundle_adjuster: " << sba_last_error() << std::endl;
 }
 
+int spherical_bundle_adjuster::do_bundle_adjustment_from_features(const std::vector<cv::KeyPoint>& left_kp,
+                                                                  const std::vector<cv::KeyPoint>& right_kp,
+                                                                  const std::vector<float>& left_desc,
+                                                                  const std::vector<float>& right_desc, int dim, int im_width,
+                                                                  int im_height) {
+  if (dim < 1 || left_desc.size() != left_kp.size() * static_cast<size_t>(dim) ||
+      right_desc.size() != right_kp.size() * static_cast<size_t>(dim))
+    return SBA_ERR_INVALID_ARG;
+  std::vector<int> query(left_kp.size()), train(left_kp.size());
+  size_t n = 0;
+  int rc = sba_match_descriptors(device, left_desc.data(), left_kp.size(), right_desc.data(), right_kp.size(), dim,
+                                 sizeof(float) * static_cast<size_t>(dim), 0.3f, nullptr, nullptr, &n, query.data(), train.data(),
+                                 nullptr);
+  if (rc) return rc;
+  std::cout << "matched : " << n << std::endl;
+  std::vector<cv::KeyPoint> valid_key_left(n), valid_key_right(n);       // feature_matcher.cpp:105-110
+  for (size_t i = 0; i < n; ++i) {
+    valid_key_left[i] = left_kp[query[i]];
+    valid_key_right[i] = right_kp[train[i]];
+  }
+  return do_bundle_adjustment_from_matches(valid_key_left, valid_key_right, static_cast<int>(n), im_width, im_height);
+}
+
 int spherical_bundle_adjuster::do_bundle_adjustment_from_matches(const std::vector<cv::KeyPoint>& left_key,
                                                                  const std::vector<cv::KeyPoint>& right_key,
                                                                  int match_size, int im_width, int im_height) {

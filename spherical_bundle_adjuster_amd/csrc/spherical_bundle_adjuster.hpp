@@ -70,6 +70,12 @@ class spherical_bundle_adjuster {
   int do_bundle_adjustment_from_matches(const std::vector<cv::KeyPoint>& left_key,
                                         const std::vector<cv::KeyPoint>& right_key, int match_size,
                                         int im_width, int im_height);
+  // The matcher's match step too (feature_matcher::match_two_image, feature_matcher.cpp:42-59, and the gather of
+  // valid_key_left / right, :105-110): exact 2-NN of the descriptors (count x dim f32 each, row-major) on the device with
+  // the reference's ratio test 0.3, then do_bundle_adjustment_from_matches on the matched key-points.
+  int do_bundle_adjustment_from_features(const std::vector<cv::KeyPoint>& left_kp, const std::vector<cv::KeyPoint>& right_kp,
+                                         const std::vector<float>& left_desc, const std::vector<float>& right_desc, int dim,
+                                         int im_width, int im_height);
   struct result {
     double rot[3] = {0, 0, 0};    // angle-axis, radians (init_rot after solve_problem)
     double tran[3] = {0, 0, 0};   // init_tran after solve_problem

@@ -9,6 +9,9 @@ The reference ships no images or fixtures, so every workload is synthetic:
   Y = R X - t, x2 = Y/|Y|, d2 = |Y| so that e = d2 x2 - d1 R x1 + t = 0 exactly at the truth
   (before noise); |t| = 1 like the output of decomposeEssentialMat
   (reference spherical_bundle_adjuster.cpp:83-85).
+* ``planted_matches``: a ``full_rt`` geometry as two sets of ERP key-points with descriptors, the matched key-points
+  sharing one random unit descriptor (plus a little noise on either side), shuffled among unmatched distractors --
+  the input of a descriptor match (feature_matcher::match_two_image).
 """
 from __future__ import annotations
 
@@ -110,3 +113,51 @@ def shard_range(n: int, rank: int, world: int) -> tuple[int, int]:
     per = -(-n // world)
     lo = min(n, rank * per)
     return lo, min(n, lo + per)
+
+
+@dataclass
+class PlantedMatches:
+    left_kp: np.ndarray        # (n_left, 7) f32 cv::KeyPoint records: pt.x, pt.y in ERP pixels, the rest 0
+    right_kp: np.ndarray       # (n_right, 7)
+    left_desc: np.ndarray      # (n_left, dim) f32
+    right_desc: np.ndarray     # (n_right, dim) f32
+    planted_left: np.ndarray   # (n,) row of match i in the left arrays
+    planted_right: np.ndarray  # (n,) row of match i in the right arrays
+    geometry: Correspondences  # the full_rt geometry the planted matches come from (rot_true, tran_true, ...)
+    im_width: int
+    im_height: int
+
+
+def sphere_to_pixels(x: np.ndarray, im_width: int, im_height: int):
+    """Unit vectors -> ERP pixel coordinates, the inverse of the reference's pixel -> sphere map (.cpp:271-298)."""
+    colat = np.arccos(np.clip(x[:, 2], -1.0, 1.0))
+    lon = np.mod(np.arctan2(x[:, 1], x[:, 0]), 2 * np.pi)
+    return lon / (2 * np.pi) * im_width, colat / np.pi * im_height
+
+
+def planted_matches(n: int, distractors_left: int = 0, distractors_right: int = 0, dim: int = 64, seed: int = BASE_SEED + 4,
+                    noise: float = 0.01, im_width: int = 3840, im_height: int = 1920, **full_rt_args) -> PlantedMatches:
+    """n matched key-points of a ``full_rt(n, seed, **full_rt_args)`` geometry in two ERP images of im_width x im_height, with
+    descriptors: both sides of a match carry the same random unit descriptor plus independent N(0, noise^2) noise per
+    component; each side also gets unmatched distractors with random unit descriptors; rows are shuffled per side.  At the
+    default noise a planted match passes the reference's ratio test (0.3) by a wide margin."""
+    c = full_rt(n, seed=seed, **full_rt_args)
+    rng = np.random.default_rng([seed, 4])
+    base = _unit(rng.standard_normal((n, dim)))
+    nl, nr = n + distractors_left, n + distractors_right
+    lx, ly = sphere_to_pixels(c.x1, im_width, im_height)
+    rx, ry = sphere_to_pixels(c.x2, im_width, im_height)
+    lpx = np.concatenate([np.stack([lx, ly], 1), rng.uniform((0, 0), (im_width, im_height), (distractors_left, 2))])
+    rpx = np.concatenate([np.stack([rx, ry], 1), rng.uniform((0, 0), (im_width, im_height), (distractors_right, 2))])
+    ld = np.concatenate([base + noise * rng.standard_normal((n, dim)), _unit(rng.standard_normal((distractors_left, dim)))])
+    rd = np.concatenate([base + noise * rng.standard_normal((n, dim)), _unit(rng.standard_normal((distractors_right, dim)))])
+    pl, pr = rng.permutation(nl), rng.permutation(nr)      # row k of a side holds item p[k]
+    il, ir = np.empty(nl, np.int64), np.empty(nr, np.int64)
+    il[pl] = np.arange(nl)
+    ir[pr] = np.arange(nr)
+    kl = np.zeros((nl, 7), np.float32)
+    kr = np.zeros((nr, 7), np.float32)
+    kl[:, :2] = lpx[pl]
+    kr[:, :2] = rpx[pr]
+    return PlantedMatches(kl, kr, np.ascontiguousarray(ld[pl], np.float32), np.ascontiguousarray(rd[pr], np.float32),
+                          il[:n], ir[:n], c, im_width, im_height)
