@@ -16,6 +16,8 @@
  *       -> sba_problem_solve()             (Levenberg-Marquardt on the host, normal equations from the GPU)
  *   - the d-only stage (spherical_bundle_adjuster.cpp:1004-1063)
  *       -> sba_problem_solve_depths()
+ *   - the joint functor over depths, rotation and translation (spherical_bundle_adjuster.cpp:843-889)
+ *       -> sba_problem_solve_joint(), sba_problem_eval_joint()
  *   - pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298)
  *       -> sba_keypoints_to_sphere()
  *   - equi2cube::get_all (equi2cube.cpp:12-302)
@@ -70,7 +72,8 @@ enum {
 enum {
   SBA_MODE_ROT = 0,  /* ba_spherical_costfunctor_rot_only  (.cpp:891-919): rot free, tran frozen */
   SBA_MODE_TRAN = 1, /* ba_spherical_costfunctor_tran_only (.cpp:947-976): tran free, rot frozen */
-  SBA_MODE_RT = 2    /* ba_spherical_costfunctor (.cpp:843-868) with d held fixed: rot+tran free */
+  SBA_MODE_RT = 2    /* ba_spherical_costfunctor (.cpp:843-868) with d held fixed: rot+tran free
+                        (d free as well: sba_problem_solve_joint) */
 };
 
 /* ---- where d1,d2 come from ----------------------------------------------------------- */
@@ -304,6 +307,37 @@ int sba_problem_solve(sba_problem* p, int mode, int depth_mode, double rot[3], d
  * rank receives its own shard's depths (at most 8 shards, see sba_problem_set_shard).                       */
 int sba_problem_solve_depths(sba_problem* p, const double rot[3], const double tran[3], double lambda,
                              double c, const sba_lm_options* opt, double* d12_out, sba_lm_summary* summary);
+
+/* ---- joint solve: depths, rotation and translation free together ------------------------ */
+/* The reference's joint functor ba_spherical_costfunctor (spherical_bundle_adjuster.cpp:843-889): one 3-residual
+ * Huber block per match over (d_i[2], rot[3], tran[3]),  e_i = d2_i x2_i - d1_i R(rot) x1_i + tran, no bounds and no
+ * regulariser (those belong to the d-only functor).  Parameters: the 2n per-match depths of the handle and the camera.
+ * The depth blocks are private to a match, so every LM iteration eliminates them per match on the device (a damped 2x2
+ * block) and solves the reduced camera system (<= 6 x 6, the Schur complement) on the host: two streaming passes per
+ * iteration, trust-region schedule as sba_problem_solve / sba_problem_solve_depths, no line search.
+ * Gauge: with SBA_TRAN_FREE the cost is homogeneous of degree 2 in (d, tran) inside Huber's quadratic region, so
+ * (d, tran) -> 0 is a minimiser.  The useful form pins |tran| with SBA_TRAN_SPHERE: opt == NULL means the defaults WITH
+ * tran_param = SBA_TRAN_SPHERE for the two entry points below; an explicit SBA_TRAN_FREE runs the functor as written.
+ * A handle with a shard, communicator, peer set or all-reduce hook, and a problem without per-match depths, is refused
+ * with SBA_ERR_UNSUPPORTED; a non-finite start with SBA_ERR_NUMERIC (the handle stays usable, its depths unchanged).
+ * Only that failure leaves the depths as they were: a solve that fails later (five invalid steps in a row, a device wait
+ * that times out and poisons the handle) leaves the last accepted depths, or an unfinished candidate, in the handle.       */
+typedef struct sba_joint_eq {     /* parameter order [rot0..2 tran0..2], unscaled, undamped camera side */
+  double S[36], gs[6];            /* reduced camera system / gradient at the given depth damping          */
+  double V[36], gc[6];            /* unreduced camera block: equals sba_problem_eval(SBA_MODE_RT, PER_MATCH) */
+  double cost, sum_w, n_outlier, gd_max;   /* gd_max: max-norm of the depth gradient                       */
+} sba_joint_eq;
+
+/* One reduce pass at (rot, tran), the uploaded depths, depth damping from `radius` (+inf: none).  The depth columns are
+ * Jacobi-scaled at this point (opt->jacobi_scaling) before min / max_lm_diagonal clamp their damping.                 */
+int sba_problem_eval_joint(sba_problem* p, const double rot[3], const double tran[3], double radius,
+                           const sba_lm_options* opt, sba_joint_eq* out);
+
+/* Joint LM from (rot, tran) and the uploaded depths.  The refined depths stay in the handle (folded planes marked
+ * stale, as sba_problem_solve_depths does) and are copied to d12_out (double[2n], may be NULL).  summary (may be NULL):
+ * num_evaluations counts device passes of either kind.                                                             */
+int sba_problem_solve_joint(sba_problem* p, double rot[3], double tran[3], const sba_lm_options* opt,
+                            sba_lm_summary* summary, double* d12_out);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

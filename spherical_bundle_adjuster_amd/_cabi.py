@@ -46,6 +46,11 @@ class NormalEq(C.Structure):
                 ("sum_w", C.c_double), ("n_outlier", C.c_double)]
 
 
+class JointEq(C.Structure):
+    _fields_ = [("S", C.c_double * 36), ("gs", C.c_double * 6), ("V", C.c_double * 36), ("gc", C.c_double * 6),
+                ("cost", C.c_double), ("sum_w", C.c_double), ("n_outlier", C.c_double), ("gd_max", C.c_double)]
+
+
 class LmOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int),
                 ("initial_trust_region_radius", C.c_double),
@@ -115,6 +120,8 @@ SIGNATURES = {
                                     C.POINTER(LmOptions), C.POINTER(LmSummary)]),
     "sba_problem_solve_depths": (C.c_int, [_vp, _dp, _dp, C.c_double, C.c_double, C.POINTER(LmOptions), _vp,
                                            C.POINTER(LmSummary)]),
+    "sba_problem_eval_joint": (C.c_int, [_vp, _dp, _dp, C.c_double, C.POINTER(LmOptions), C.POINTER(JointEq)]),
+    "sba_problem_solve_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(LmSummary), _vp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

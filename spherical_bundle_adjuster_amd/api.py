@@ -27,6 +27,19 @@ class NormalEquations:
 
 
 @dataclass
+class JointEquations:
+    """One reduce pass of the joint solve (Problem.eval_joint), parameter order [rot | tran], unscaled camera side."""
+    S: np.ndarray          # (6, 6) reduced camera system sum (w F^T F - W^T U^-1 W) at the given depth damping
+    gs: np.ndarray         # (6,)   reduced gradient
+    V: np.ndarray          # (6, 6) unreduced camera block = eval(MODE_RT, DEPTH_PER_MATCH).H
+    gc: np.ndarray         # (6,)
+    cost: float
+    sum_w: float
+    n_outlier: float
+    gd_max: float          # max-norm of the depth gradient
+
+
+@dataclass
 class SolveSummary:
     termination: str
     num_iterations: int
@@ -387,6 +400,31 @@ class Problem:
                                                                  C.byref(opt), out.ctypes.data_as(C.c_void_p),
                                                                  C.byref(s)))
         return out, _summary(s)
+
+    # -- joint solve: depths, rotation and translation together ---------------------------------------
+    def eval_joint(self, rot, tran, radius=float("inf"), options: cabi.LmOptions | None = None) -> JointEquations:
+        """One reduce pass of the joint solve at (rot, tran) and the handle's depths; `radius` sets the depth damping
+        (inf: none).  options None = the defaults with tran_param = TRAN_SPHERE."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        eq = cabi.JointEq()
+        cabi.check(self._lib, self._lib.sba_problem_eval_joint(self._h, _dptr(rot), _dptr(tran), float(radius),
+                                                               None if options is None else C.byref(options), C.byref(eq)))
+        a = lambda v, shape: np.array(v, dtype=np.float64).reshape(shape)
+        return JointEquations(a(eq.S, (6, 6)), a(eq.gs, (6,)), a(eq.V, (6, 6)), a(eq.gc, (6,)), float(eq.cost), float(eq.sum_w),
+                              float(eq.n_outlier), float(eq.gd_max))
+
+    def solve_joint(self, rot, tran, options: cabi.LmOptions | None = None, return_depths: bool = True):
+        """Joint LM over the handle's per-match depths and the camera from (rot, tran): the reference's joint functor.  The
+        refined depths stay in the handle.  options None = the defaults with tran_param = TRAN_SPHERE (|tran| pinned: the
+        gauge of the problem).  Returns (rot, tran, d12 (n, 2) or None, SolveSummary); inputs are not modified."""
+        rot = _f64(rot, (3,)).copy()
+        tran = _f64(tran, (3,)).copy()
+        out = np.zeros((self.size, 2)) if return_depths else None
+        s = cabi.LmSummary()
+        cabi.check(self._lib, self._lib.sba_problem_solve_joint(self._h, _dptr(rot), _dptr(tran),
+                                                                None if options is None else C.byref(options), C.byref(s),
+                                                                None if out is None else out.ctypes.data_as(C.c_void_p)))
+        return rot, tran, out, _summary(s)
 
     # -- 8-point initial guess ----------------------------------------------------------------------
     def epipolar_moments(self) -> np.ndarray:

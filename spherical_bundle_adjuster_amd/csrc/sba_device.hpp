@@ -7,6 +7,7 @@
 
 #include "../../include/sba_hip.h"
 #include "sba_depth_solver.hpp"
+#include "sba_joint_solver.hpp"
 #include "sba_rotation.hpp"
 
 namespace sba {
@@ -374,6 +375,29 @@ hipError_t launch_batch_dyn_compact(BatchDynCtl* ctl, unsigned int* active, cons
 hipError_t launch_batch_depth_finish(int store, const PairDesc* desc, const unsigned char* flip_dev, int num_pairs, double* a1,
                                      double* a2, const double* b1, const double* b2, const unsigned long long* offsets_dev,
                                      double* out_dev, hipStream_t stream);
+
+// Joint solve (reference .cpp:843-889; sba_joint.hip, step logic sba_joint_solver.hpp): one pass of either kind.
+struct JointParams {
+  SweepParams cur;       // the current camera (per-match form: Rn = -R, Gn unused), Huber delta, n
+  SweepParams cand;      // step pass: the candidate camera (Rn, t)
+  double J[9];           // frame of the rotation Jacobian A = -[a]x J (factored_frame: J_l, or I at small angles)
+  double delta_c[6];     // step pass: ambient camera step [rot | tran]
+  double inv_radius;     // depth damping D / radius; 0 = none
+  double min_diagonal, max_diagonal;
+  int small_angle;       // rot.rot <= DBL_EPSILON: a = -d1 x1 instead of v
+  int first;             // reduce pass: compute and store the depth Jacobi scaling (else it is read)
+  int jacobi_scaling;
+  int pad_;
+};
+// Results: the JOINT_OUT_* / JOINT_STEP_* slots (sba_joint_solver.hpp) in out (device) and, with host_out (mapped host
+// memory, JOINT_ROW + 1 words), published there followed by `seq` at host_out[JOINT_ROW].  partials: [grid][JOINT_ROW].
+hipError_t joint_blocks_per_cu(int store, int* blocks);   // resident 256-thread blocks per CU of joint_reduce_kernel
+hipError_t launch_joint_reduce(int store, const Planes& pl, const double* d1, const double* d2, double* sc1, double* sc2,
+                               const JointParams& prm, double* partials, int grid, double* out, double* host_out,
+                               unsigned long long seq, hipStream_t stream);
+hipError_t launch_joint_step(int store, const Planes& pl, const double* d1, const double* d2, double* c1, double* c2,
+                             const double* sc1, const double* sc2, const JointParams& prm, double* partials, int grid,
+                             double* out, double* host_out, unsigned long long seq, hipStream_t stream);
 
 // 8-point initial guess, device part (.cpp:53-68): A^T A of the kron(left, right) rows for 64 interleaved groups.
 // groups_dev: [64][45]; partials: [grid][45][64] scratch.

@@ -1,5 +1,7 @@
 // Command-line driver with the reference's argument contract (main/main.cpp:8-27):
-//   sba_main <L> <R> <exp roll> <exp pitch> <exp yaw> <exp Tx> <exp Ty> <exp Tz> <exp d>
+//   sba_main [--joint] <L> <R> <exp roll> <exp pitch> <exp yaw> <exp Tx> <exp Ty> <exp Tz> <exp d>
+// --joint (anywhere on the line; not in the reference): refine depths, rotation and translation together after the
+// tran-only stage (spherical_bundle_adjuster::set_joint_refinement).  Without it the run is the reference's three stages.
 // With OpenCV (SBA_WITH_OPENCV) <L>/<R> are ERP images and a matcher must be linked in by the
 // integrator.  Without OpenCV <L>/<R> are files of cv::KeyPoint records (28 bytes
 // each) preceded by a 16-byte header {int32 count, int32 im_width, int32 im_height, int32 dim}:
@@ -10,6 +12,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <thread>
@@ -32,6 +35,15 @@ bool read_keypoints(const char* path, std::vector<cv::KeyPoint>* out, std::vecto
 }  // namespace
 
 int main(int argc, char** argv) {
+  bool joint = false;
+  {
+    int kept = 1;
+    for (int i = 1; i < argc; ++i) {
+      if (std::strcmp(argv[i], "--joint") == 0) joint = true;
+      else argv[kept++] = argv[i];
+    }
+    argc = kept;
+  }
   if (argc != 10) {
     std::cout << "usage : spherical_bundle_adjuster.out <L image> <R image> <exp roll> <exp pitch> <exp yaw> "
                  "<exp Tx> <exp Ty> <exp Tz> <exp d>" << std::endl;
@@ -42,6 +54,7 @@ int main(int argc, char** argv) {
   sph_ba.set_omp(static_cast<int>(std::max(1u, std::thread::hardware_concurrency())));   // omp_get_num_procs(), main/main.cpp:31
   // SBA_INITIAL_GUESS=0: start from the expected values on the command line instead of the 8-point consensus
   if (const char* env = std::getenv("SBA_INITIAL_GUESS")) sph_ba.set_initial_guess(env[0] != '0');
+  sph_ba.set_joint_refinement(joint);
   std::vector<cv::KeyPoint> left_key, right_key;
   std::vector<float> left_desc, right_desc;
   int w = 0, h = 0, w2 = 0, h2 = 0, dim = 0, dim2 = 0;

@@ -3,6 +3,7 @@
 //   sba_transport.cpp  multi-GPU transports: RCCL (bound at run time), direct peer exchange, user hook; pack all-reduce
 //   sba_stages.cpp     d-only stage and 8-point initial guess entry points
 //   sba_select.cpp     per-match residuals and compaction of the matches
+//   sba_joint.cpp      joint solve (depths, rotation and translation together) entry points
 // Internal: nothing here is exported from the library.
 #pragma once
 #include <cstdlib>
@@ -34,6 +35,10 @@ struct sba_problem {
   void* upload_pinned[2] = {nullptr, nullptr};   // large uploads: two pinned staging buffers (sba_shim.cpp: upload_common)
   void* depth_scratch = nullptr;   // d-only stage: candidate + scaling planes, block partials, results; kept across calls
   size_t depth_scratch_bytes = 0;
+  double* joint_host = nullptr;    // joint solve: mapped pinned row the finalize kernel publishes to (JOINT_ROW doubles + the
+  double* joint_host_dev = nullptr;  // sequence word); allocated by the first joint call.  Its device planes share depth_scratch
+  unsigned long long joint_seq = 0;
+  int joint_occ[2] = {0, 0};       // resident blocks per CU of joint_reduce_kernel per [store]
   void* subset_scratch = nullptr;  // reference sampling: [trials][45] moments, then the [trials][m] index lists; kept across calls
   size_t subset_scratch_bytes = 0;
   void* select_scratch = nullptr;  // per-match residuals: inlier count, then the requested outputs; kept across calls

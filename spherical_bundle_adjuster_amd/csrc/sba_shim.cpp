@@ -672,6 +672,7 @@ int sba_problem_destroy(sba_problem* p) {
   if (p->select_scratch) (void)hipFree(p->select_scratch);
   if (p->depth_scratch) (void)hipFree(p->depth_scratch);
   if (p->pack_host) (void)hipHostFree(p->pack_host);
+  if (p->joint_host) (void)hipHostFree(p->joint_host);
   if (p->res_rec) (void)hipHostFree(p->res_rec);
   if (p->small_rec) (void)hipHostFree(p->small_rec);
   for (void* q : p->upload_pinned) if (q) (void)hipHostFree(q);

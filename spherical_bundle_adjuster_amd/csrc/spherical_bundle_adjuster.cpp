@@ -199,6 +199,17 @@ int spherical_bundle_adjuster::solve_problem(sba_lm_options& opt, std::vector<cv
   if (rc) return rc;
   report("tran-only", res.tran_stage);
 
+  // optional stage 4 (set_joint_refinement): depths, rotation and translation together, from the staged result.  The
+  // handle still holds the d-only stage's depths; the sphere parameterisation keeps |tran| at its current length.
+  res.joint_stage = sba_lm_summary{};
+  if (joint_refinement && match_num > 0) {
+    sba_lm_options jopt = opt;
+    jopt.tran_param = SBA_TRAN_SPHERE;
+    rc = sba_problem_solve_joint(problem, init_rot, init_tran, &jopt, &res.joint_stage, reinterpret_cast<double*>(init_d.data()));
+    if (rc) return rc;
+    report("joint", res.joint_stage);
+  }
+
   std::cout << "expected rotation vector " << expected_roll << ' ' << expected_pitch << ' ' << expected_yaw << ' ' << std::endl;
   std::cout << "rotation vector in degree " << init_rot[0] / kPi * 180.0 << ' ' << init_rot[1] / kPi * 180.0 << ' '
             << init_rot[2] / kPi * 180.0 << std::endl;

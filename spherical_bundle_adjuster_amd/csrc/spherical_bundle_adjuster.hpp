@@ -65,6 +65,11 @@ class spherical_bundle_adjuster {
   enum guess_sampling_t { GUESS_AUTO = 0, GUESS_GROUPS = 1, GUESS_REFERENCE = 2 };
   static constexpr int kReferenceSamplingMaxN = 65536;
   void set_guess_sampling(guess_sampling_t s) { guess_sampling = s; }
+  // Joint refinement after the tran-only stage (default off: do_bundle_adjustment* behaves exactly like the reference's
+  // three stages).  On: the reference's joint functor (.cpp:843-889) over the depths solved by the d-only stage and the
+  // pose of the rot / tran stages, |tran| pinned at its current length (SBA_TRAN_SPHERE: the problem's gauge) --
+  // sba_problem_solve_joint.  The printed pose, the log row and the depth log then carry the refined values.
+  void set_joint_refinement(bool on) { joint_refinement = on; }
   // Everything after the matcher: pixel -> sphere, initial values, three-stage solve, log row.
   // Returns 0 or a negative SBA_ERR_* (message via sba_last_error()).
   int do_bundle_adjustment_from_matches(const std::vector<cv::KeyPoint>& left_key,
@@ -81,6 +86,7 @@ class spherical_bundle_adjuster {
     double tran[3] = {0, 0, 0};   // init_tran after solve_problem
     int match_size = 0;
     sba_lm_summary depth_stage{}, rot_stage{}, tran_stage{};
+    sba_lm_summary joint_stage{};  // all zero unless set_joint_refinement(true)
     int guess_candidates = 0;     // valid rotation candidates of the 8-point consensus
   };
   const result& last_result() const { return res; }
@@ -101,6 +107,7 @@ class spherical_bundle_adjuster {
   bool use_initial_guess = true;
   unsigned long long guess_seed = 0;
   guess_sampling_t guess_sampling = GUESS_AUTO;
+  bool joint_refinement = false;
   const void* resident_left = nullptr;   // coordinates currently resident in `problem`
   int resident_n = -1;
   sba_problem* problem = nullptr;
