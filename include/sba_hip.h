@@ -521,6 +521,31 @@ int sba_batch_solve_problem(sba_batch* b, int use_initial_guess, int trials, dou
 int sba_batch_solve_depths(sba_batch* b, const double* rot, const double* tran, double lambda, double c,
                            const sba_lm_options* opt, double* d12_out, sba_lm_summary* summaries, int* status);
 
+/* The joint solve (sba_problem_eval_joint / sba_problem_solve_joint: the reference's joint functor, .cpp:843-889) for EVERY pair
+ * of the batch, on the batch's resident planes.  rot, tran: double[num_pairs][3].  opt == NULL means the defaults with
+ * tran_param = SBA_TRAN_SPHERE (the gauge), as for the single-problem entry points; an explicit SBA_TRAN_FREE runs the
+ * functor as written.  A batch without per-match depths is refused with SBA_ERR_UNSUPPORTED, a poisoned handle and one that was
+ * never uploaded as everywhere; SBA_PUBLISH=0 is refused with SBA_ERR_UNSUPPORTED as by sba_batch_solve_depths.  One 256-thread
+ * block per pair (the reduce pass needs one wave per SIMD to itself): made for batches of many pairs; a batch of a few huge pairs
+ * is served, but by as many CUs as it has pairs.  A pair's sums are formed in an order that depends on its own matches only:
+ * its results are the same bits alone in a batch, among other pairs, and in either pair layout.
+ * sba_batch_eval_joint: one reduce pass per pair at (rot[g], tran[g]) and the batch's depths, depth damping from `radius`
+ * (> 0, +inf: none; otherwise SBA_ERR_INVALID_ARG); out: sba_joint_eq[num_pairs] -- pair g's equals sba_problem_eval_joint on
+ * pair g alone up to the summation order; an empty pair gives a zero system.                                                */
+int sba_batch_eval_joint(sba_batch* b, const double* rot, const double* tran, double radius, const sba_lm_options* opt,
+                         sba_joint_eq* out);
+/* sba_batch_solve_joint: one joint LM per pair from (rot[g], tran[g]) -- in / out -- and the batch's depths.  The refined depths
+ * stay in the batch's depth planes (a following SBA_DEPTH_PER_MATCH eval, solve, residuals or compaction sees them) and are
+ * copied to d12_out (may be NULL; indexed like the uploaded d12, as sba_batch_solve_depths).  summaries / status (may be NULL)
+ * as sba_batch_solve: status[g] is SBA_OK or SBA_ERR_NUMERIC, the call returns SBA_ERR_NUMERIC when any pair failed and the
+ * other pairs' results are valid.  A pair whose start is non-finite fails that way with its depths, rot and tran unchanged.
+ * An empty pair terminates at once on the gradient test, rot / tran unchanged.  The solvers run on the device, the whole solve
+ * is one launch (the block that owns a pair keeps the pair's solver in LDS; at most 2 * max_num_iterations + 2 passes per pair,
+ * a pair that would need more is reported with SBA_ERR_NUMERIC).  SBA_BATCH_DEVICE_JOINT=0: host solvers in lock-step, one
+ * launch per pass -- the two drivers agree to the bit.                                                                        */
+int sba_batch_solve_joint(sba_batch* b, double* rot, double* tran, const sba_lm_options* opt, sba_lm_summary* summaries,
+                          int* status, double* d12_out);
+
 /* ---- single matches of a batch: residuals, inlier sets, compaction ---- */
 /* Rows r = 0 .. total - 1 with total = offsets[num_pairs] - offsets[0] of the current layout; row r is the caller's row
  * offsets[0] + r.  rot, tran, d1, d2 as for sba_batch_eval (per pair; NULL depths mean 1.0; ignored with

@@ -780,12 +780,46 @@ class Batch:
         return d12, [_summary(sums[i]) for i in range(self.num_pairs)], status[:self.num_pairs]
 
 
+    # -- joint solve: every pair's depths, rotation and translation together ----------------------------
+    def eval_joint(self, rot, tran, radius=float("inf"), options: cabi.LmOptions | None = None):
+        """One reduce pass of the joint solve per pair at (rot[g], tran[g]) and the batch's depths; `radius` sets the depth
+        damping (inf: none).  options None = the defaults with tran_param = TRAN_SPHERE.  Returns a list of JointEquations."""
+        rot, rp = self._pp(rot, 3)
+        tran, tp = self._pp(tran, 3)
+        eqs = (cabi.JointEq * max(self.num_pairs, 1))()
+        cabi.check(self._lib, self._lib.sba_batch_eval_joint(self._h, rp, tp, float(radius),
+                                                             None if options is None else C.byref(options), eqs))
+        a = lambda v, shape: np.array(v, dtype=np.float64).reshape(shape)
+        return [JointEquations(a(e.S, (6, 6)), a(e.gs, (6,)), a(e.V, (6, 6)), a(e.gc, (6,)), float(e.cost), float(e.sum_w),
+                               float(e.n_outlier), float(e.gd_max)) for e in eqs[:self.num_pairs]]
+
+    def solve_joint(self, rot, tran, options: cabi.LmOptions | None = None, return_depths: bool = True, check: bool = True):
+        """Joint LM per pair over the batch's per-match depths and the pair's camera from (rot[g], tran[g]): the reference's
+        joint functor for every pair.  The refined depths stay in the batch.  options None = the defaults with tran_param =
+        TRAN_SPHERE (|tran| pinned per pair).  Returns (rot (B, 3), tran (B, 3), d12 (offsets[-1], 2) or None, [SolveSummary],
+        status (B,)); inputs are not modified.  check=False: pairs that failed are reported in status only."""
+        B = self.num_pairs
+        rot = _f64(rot).reshape(B, 3).copy()
+        tran = _f64(tran).reshape(B, 3).copy()
+        d12 = np.zeros((int(self._total), 2)) if return_depths else None
+        sums = (cabi.LmSummary * max(B, 1))()
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        rc = self._lib.sba_batch_solve_joint(self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options), sums,
+                                             status.ctypes.data_as(C.POINTER(C.c_int)),
+                                             None if d12 is None else d12.ctypes.data_as(C.c_void_p))
+        if check or rc != cabi.SBA_ERR_NUMERIC:
+            cabi.check(self._lib, rc)
+        return rot, tran, d12, [_summary(sums[i]) for i in range(B)], status[:B]
+
     def solve_problem(self, rot=None, tran=None, use_initial_guess: bool = True, trials: int = 80, subset_fraction: float = 0.25,
-                      seed: int = 0, options: cabi.LmOptions | None = None, want_depths: bool = False, check: bool = True):
+                      seed: int = 0, options: cabi.LmOptions | None = None, want_depths: bool = False, check: bool = True,
+                      joint: bool = False):
         """The reference's per-pair pipeline for every pair (initial guess -> d-only -> rot-only -> tran-only,
         reference .cpp:302-331, :183-217).  rot / tran: start values (B, 3) (needed when use_initial_guess is False; with the
         guess they only serve pairs that have no valid candidate).  Returns a dict: rot, tran (B, 3), d_uniform (B, 2),
-        guess_candidates (B,), depth / rot / tran stage summaries, status (B,), d12 (if want_depths)."""
+        guess_candidates (B,), depth / rot / tran stage summaries, status (B,), d12 (if want_depths).
+        joint=True: solve_joint() follows the tran-only stage, from that stage's rot / tran and the refined depths; the dict
+        then also holds joint_rot, joint_tran (B, 3), joint_stage summaries, joint_status (B,) and joint_d12 (if want_depths)."""
         B = self.num_pairs
         r = np.zeros((max(B, 1), 3)) if rot is None else _f64(rot).reshape(B, 3).copy()
         t = np.zeros((max(B, 1), 3)) if tran is None else _f64(tran).reshape(B, 3).copy()
@@ -802,10 +836,14 @@ class Batch:
         seconds = time.perf_counter() - t0       # the library call alone (the summaries below are 3 B Python objects)
         if check or rc != cabi.SBA_ERR_NUMERIC:
             cabi.check(self._lib, rc)
-        return {"rot": r[:B], "tran": t[:B], "d_uniform": du[:B], "guess_candidates": nc[:B], "status": status[:B], "d12": d12,
+        res = {"rot": r[:B], "tran": t[:B], "d_uniform": du[:B], "guess_candidates": nc[:B], "status": status[:B], "d12": d12,
                 "seconds_inside_the_library": seconds,
                 "depth_stage": [_summary(sums[0][i]) for i in range(B)], "rot_stage": [_summary(sums[1][i]) for i in range(B)],
                 "tran_stage": [_summary(sums[2][i]) for i in range(B)]}
+        if joint:
+            jr, jt, jd, js, jst = self.solve_joint(r[:B], t[:B], return_depths=want_depths, check=check)
+            res.update(joint_rot=jr, joint_tran=jt, joint_d12=jd, joint_stage=js, joint_status=jst)
+        return res
 
     def epipolar_moments(self):
         """Group moments of every pair: (B, 64, 45)."""

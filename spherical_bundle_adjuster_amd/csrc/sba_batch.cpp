@@ -40,6 +40,9 @@ int free_batch_data(sba_batch* b) {
   if (b->depth_const_dev) SBA_TRY_HIP(hipFree(b->depth_const_dev));
   if (b->depth_pass_host) SBA_TRY_HIP(hipHostFree(b->depth_pass_host));
   if (b->depth_out_host) SBA_TRY_HIP(hipHostFree(b->depth_out_host));
+  if (b->joint_pass_host) SBA_TRY_HIP(hipHostFree(b->joint_pass_host));
+  if (b->joint_out_host) SBA_TRY_HIP(hipHostFree(b->joint_out_host));
+  b->joint_pass_host = nullptr; b->joint_pass_host_dev = nullptr; b->joint_out_host = nullptr; b->joint_out_host_dev = nullptr; b->joint_seq = 0;
   if (b->epi_groups_dev) SBA_TRY_HIP(hipFree(b->epi_groups_dev));
   if (b->epi_groups_host) SBA_TRY_HIP(hipHostFree(b->epi_groups_host));
   if (b->offsets_dev) SBA_TRY_HIP(hipFree(b->offsets_dev));
@@ -85,6 +88,27 @@ void write_state(sba_batch* b, const double* rot, const double* tran, const doub
     st.n = (!active || active[g]) ? b->n[g] : 0;
     st.pad_ = 0;
   }
+}
+
+int ensure_depth_work(sba_batch* b) {
+  if (b->depth_work) return SBA_OK;
+  const int B = b->num_pairs;
+  const size_t elems = b->plane_elems;
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->depth_work), 4 * elems * sizeof(double)));
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->depth_const_dev), sizeof(sba::BatchDepthConst) * B));
+  SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->depth_pass_host), sizeof(sba::BatchDepthPass) * B,
+                            hipHostMallocMapped | hipHostMallocCoherent));
+  SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->depth_pass_host_dev), b->depth_pass_host, 0));
+  SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->depth_out_host), sizeof(double) * (static_cast<size_t>(B) * sba::DEPTH_ROW + 8),
+                            hipHostMallocMapped | hipHostMallocCoherent));
+  std::memset(b->depth_out_host, 0, sizeof(double) * (static_cast<size_t>(B) * sba::DEPTH_ROW + 8));
+  SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->depth_out_host_dev), b->depth_out_host, 0));
+  b->depth_seq = 0;
+  // candidate + scaling planes start zeroed, once: a candidate plane becomes a pair's depth plane when a step is accepted,
+  // and its padding must be zeros like the uploaded planes' -- the passes only ever write real elements (and zeros into the
+  // padding element of an odd-sized pair), so the padding stays zero from stage to stage
+  SBA_TRY_HIP(hipMemsetAsync(b->depth_work, 0, 4 * elems * sizeof(double), b->stream));
+  return SBA_OK;
 }
 
 int layout_pairs(sba_batch* b, const size_t* offsets, int num_pairs, int store, bool has_d12) {
@@ -624,22 +648,7 @@ int batch_solve_depths_impl(sba_batch* b, const double* rot, const double* tran,
   if (opt) o = *opt; else sba::lm_default_options(&o);
   const auto t_start = std::chrono::steady_clock::now();
   const size_t elems = b->plane_elems;
-  if (!b->depth_work) {
-    SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->depth_work), 4 * elems * sizeof(double)));
-    SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&b->depth_const_dev), sizeof(sba::BatchDepthConst) * B));
-    SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->depth_pass_host), sizeof(sba::BatchDepthPass) * B,
-                              hipHostMallocMapped | hipHostMallocCoherent));
-    SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->depth_pass_host_dev), b->depth_pass_host, 0));
-    SBA_TRY_HIP(hipHostMalloc(reinterpret_cast<void**>(&b->depth_out_host), sizeof(double) * (static_cast<size_t>(B) * sba::DEPTH_ROW + 8),
-                              hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(b->depth_out_host, 0, sizeof(double) * (static_cast<size_t>(B) * sba::DEPTH_ROW + 8));
-    SBA_TRY_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&b->depth_out_host_dev), b->depth_out_host, 0));
-    b->depth_seq = 0;
-    // candidate + scaling planes start zeroed, once: a candidate plane becomes a pair's depth plane when a step is accepted,
-    // and its padding must be zeros like the uploaded planes' -- the passes only ever write real elements (and zeros into the
-    // padding element of an odd-sized pair), so the padding stays zero from stage to stage
-    SBA_TRY_HIP(hipMemsetAsync(b->depth_work, 0, 4 * elems * sizeof(double), b->stream));
-  }
+  { const int _rc = sba::batch::ensure_depth_work(b); if (_rc) return _rc; }
   double *w1 = b->depth_work, *w2 = w1 + elems, *sc1 = w1 + 2 * elems, *sc2 = w1 + 3 * elems;
   std::vector<sba::BatchDepthConst> cst(B);
   for (int g = 0; g < B; ++g) {

@@ -51,6 +51,12 @@ struct sba_batch {
   double* depth_out_host = nullptr;           // pinned + mapped: [num_pairs][16] results, then the sequence word
   double* depth_out_host_dev = nullptr;
   unsigned long long depth_seq = 0;
+  // batched joint solve (allocated on first use; its work planes are the d-only stage's: depth_work)
+  sba::BatchJointPass* joint_pass_host = nullptr;     // pinned + mapped: the lock-step driver's per-pair pass records
+  sba::BatchJointPass* joint_pass_host_dev = nullptr;
+  double* joint_out_host = nullptr;           // pinned + mapped: [num_pairs][JOINT_ROW] rows, then the sequence word
+  double* joint_out_host_dev = nullptr;
+  unsigned long long joint_seq = 0;
   // batched initial guess (allocated on first use): the 64 x 45 group moments of every pair
   double* epi_groups_dev = nullptr;
   double* epi_groups_host = nullptr;          // pinned
@@ -92,6 +98,9 @@ void write_state(sba_batch* b, const double* rot, const double* tran, const doub
 // the descriptors and the row offsets (relative to offsets[0]) on the device, and the per-pair mapped buffers.  The handle
 // must hold no pair data (free_batch_data).  An upload and a compaction both lay out a batch through here.
 int layout_pairs(sba_batch* b, const size_t* offsets, int num_pairs, int store, bool has_d12);
+// The work planes (candidate depths, depth Jacobi scaling: zeroed once) and the per-pair buffers of the batched d-only stage,
+// allocated on first use; the batched joint solve shares the planes (the two stages never overlap).
+int ensure_depth_work(sba_batch* b);
 
 }  // namespace batch
 }  // namespace sba

@@ -399,6 +399,43 @@ hipError_t launch_joint_step(int store, const Planes& pl, const double* d1, cons
                              const double* sc1, const double* sc2, const JointParams& prm, double* partials, int grid,
                              double* out, double* host_out, unsigned long long seq, hipStream_t stream);
 
+// Batched joint solve (sba_batch_joint.hip): ONE 256-thread block per pair -- the reduce body's ~350 registers fit one wave per
+// SIMD only, a 512-thread block would halve the budget and spill into the hot loop.  BatchJointPass: what the lock-step driver
+// hands over per pair and pass (mapped pinned host memory): the pass kind (kJointReduce / kJointStep), the current camera, for a
+// step pass the candidate camera and the ambient camera step, the radius of the depth damping, flags (bit 0 first pass: store
+// the depth Jacobi scaling, bit 3 flip: the pair's current depths are in the work planes, its candidates go to the batch's depth
+// planes), n = matches taking part (0: skip the pair).  Thread 0 of the pair's block turns the record into the pass's
+// JointParams ON THE DEVICE (fill_sweep_params, factored_frame) -- as thread 0 of batch_joint_solve_kernel does from its solver's
+// request, so both drivers run their passes from the same bits.  Results: out_host[pair][JOINT_ROW] (JOINT_OUT_* / JOINT_STEP_*
+// slots; zeros for a skipped pair) in mapped host memory, then `seq` at out_host[num_pairs * JOINT_ROW].
+struct BatchJointPass {
+  double rot[3], tran[3];
+  double rot_cand[3], tran_cand[3];
+  double delta_c[6];
+  double radius;
+  unsigned long long n;
+  unsigned int kind, flags;
+};
+static_assert(sizeof(BatchJointPass) == 168, "BatchJointPass layout");
+hipError_t launch_batch_joint_pass(int store, const Planes& pl, const PairDesc* desc, const BatchJointPass* pass_host_dev, int num_pairs,
+                                   const sba_lm_options& opt, double* a1, double* a2, double* b1, double* b2, double* sc1, double* sc2,
+                                   double* out_host_dev, unsigned int* ticket, unsigned long long seq, hipStream_t stream);
+// The whole joint LM of every pair in one launch (batch_joint_solve_kernel: one JointSolver per pair in LDS).  io: the mapped
+// per-pair records of the batch -- in: rot, tran, status != 0 marks a pair that must not start (non-finite start); out: rot,
+// tran, summary, status, pad_ = passes run.  (a1, a2): the batch's depth planes, (b1, b2): candidate work planes; offsets_dev /
+// out_dev as for launch_batch_depth_finish (out_dev may be null); seq_host_dev receives `seq` once every pair has delivered.
+hipError_t launch_batch_joint_solve(int store, const Planes& pl, const PairDesc* desc, int num_pairs, const sba_lm_options& opt,
+                                    double* a1, double* a2, double* b1, double* b2, double* sc1, double* sc2,
+                                    const unsigned long long* offsets_dev, double* out_dev, BatchLmIo* io, unsigned int* ticket,
+                                    unsigned long long* seq_host_dev, unsigned long long seq, hipStream_t stream);
+// Passes a pair's joint solve can need: in JointSolver::feed_reduce every reduce pass either finishes the solve or increments
+// the iteration counter (which max_num_iterations bounds), and an iteration has at most one step pass.
+inline int batch_joint_pass_bound(const sba_lm_options& opt) {
+  long long its = opt.max_num_iterations > 0 ? opt.max_num_iterations : 0;
+  if (its > (1ll << 23)) its = 1ll << 23;
+  return static_cast<int>(2 * its + 2);
+}
+
 // 8-point initial guess, device part (.cpp:53-68): A^T A of the kron(left, right) rows for 64 interleaved groups.
 // groups_dev: [64][45]; partials: [grid][45][64] scratch.
 hipError_t launch_epipolar_moments(int store, const Planes& pl, size_t n, double* partials, int grid,

@@ -30,6 +30,14 @@
 #pragma STDC FP_CONTRACT OFF
 #endif
 
+// On the device the solver lives in LDS and is fed from inside a kernel (sba_batch_joint.hip): feed() is inlined into every
+// kernel that calls it, a call would put a stack frame into scratch memory.  The host build is not affected.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SBA_JOINT_FEED_INLINE __attribute__((always_inline))
+#else
+#define SBA_JOINT_FEED_INLINE
+#endif
+
 namespace sba {
 
 // Row of a reduce pass: [0..23] the unreduced camera block in SBA_PACK_* layout (sum w F^T F, sum w F^T e, cost, outliers),
@@ -104,7 +112,7 @@ class JointSolver {
   SBA_HD bool take_candidate() { const bool s = swap_; swap_ = false; return s; }
 
   // `row`: the reductions of the requested pass (JOINT_OUT_* / JOINT_STEP_* slots).
-  SBA_HD void feed(const double* row) {
+  SBA_HD SBA_JOINT_FEED_INLINE void feed(const double* row) {
     if (done_) return;
     sum_.num_evaluations++;
     if (rq_.kind == kJointReduce) feed_reduce(row); else feed_step(row);
