@@ -246,6 +246,25 @@ int sba_problem_residuals(sba_problem* p, int depth_mode, const double rot[3], c
  * still sum over the union.  On an error the handle may be left without correspondences (SBA_ERR_NOT_UPLOADED after).  */
 int sba_problem_compact(sba_problem* p, const unsigned char* keep, size_t* n_kept, long long* kept_index);
 
+/* ---- order statistics of the squared residual norms, and an inlier cut taken from them ---- */
+/* values[j] = the ranks[j]-th smallest (0-based: rank 0 is the minimum, n - 1 the maximum) of s_i = e_i.e_i, the sq_norm of
+ * sba_problem_residuals at the same arguments, selected on the device: the s plane is written by the same kernel, so every
+ * value is, bit for bit, an element of that array, and no interpolation happens.  1 <= num_ranks <= 8, every ranks[j] < n,
+ * n > 0.  Order is that of the bit patterns read as unsigned 64-bit integers: numeric for s >= +0, and every NaN (either
+ * sign) sorts above +inf.  Exact radix select with integer counts: the same bits on every run and for every grid size.
+ * Replaces sba_problem_residuals(sq_norm) + a partition of the n doubles on the host.  A handle that is sharded, hooked or
+ * connected to peers is refused with SBA_ERR_UNSUPPORTED (the shards' histograms are not summed).                        */
+int sba_problem_residual_order_stats(sba_problem* p, int depth_mode, const double rot[3], const double tran[3], double d1,
+                                     double d2, const size_t* ranks, int num_ranks, double* values);
+/* *threshold = scale * s_(rank) (one IEEE f64 multiplication; scale finite and >= 0), then the matches with
+ * s_i <= *threshold stay, through the compaction of sba_problem_compact: afterwards the handle is what a fresh upload of the
+ * kept matches with the same store would be, *n_kept is their number and kept_index (may be NULL; capacity n) receives their
+ * original indices in order.  A match whose s is NaN is dropped -- unlike `inlier` of sba_problem_residuals, where a NaN
+ * counts as inside.  The flags stay on the device.  Replaces sba_problem_residuals(sq_norm) + a host partition +
+ * sba_problem_compact with a host-built mask.  Arguments and refusals as for sba_problem_residual_order_stats.           */
+int sba_problem_keep_below(sba_problem* p, int depth_mode, const double rot[3], const double tran[3], double d1, double d2,
+                           size_t rank, double scale, double* threshold, size_t* n_kept, long long* kept_index);
+
 /* ---- one residual + Jacobian sweep ------------------------------------------------------ */
 /* Evaluates all local correspondences at (rot, tran), reduces on the device, all-reduces if a
  * communicator/hook is installed, and returns the expanded normal equations.  depth_mode
@@ -571,6 +590,20 @@ int sba_batch_compact(sba_batch* b, const unsigned char* keep, size_t* n_kept, l
  * the per-pair counts come back before the new layout (and the kept row numbers, if asked for).                        */
 int sba_batch_keep_inliers(sba_batch* b, int depth_mode, const double* rot, const double* tran, const double* d1,
                            const double* d2, double huber_delta, size_t* n_kept, long long* kept_index);
+/* sba_problem_residual_order_stats for every pair at its own (rot, tran, d1, d2), all pairs in the same launches: pair g
+ * selects among its own n[g] rows of sba_batch_residuals' sq_norm.  ranks and values: [num_pairs][num_ranks], ranks[g][j] <
+ * n[g]; an empty pair takes no part, its ranks are not looked at and its values are NaN.  A pair's values do not depend on
+ * the other pairs.  Replaces sba_batch_residuals(sq_norm) + one host partition per pair.                                */
+int sba_batch_residual_order_stats(sba_batch* b, int depth_mode, const double* rot, const double* tran, const double* d1,
+                                   const double* d2, const size_t* ranks, int num_ranks, double* values);
+/* threshold[g] = scale[g] * s_(rank[g]) of pair g (NaN for an empty pair), then every pair keeps its rows with
+ * s <= threshold[g] (a NaN s is dropped) through the compaction of sba_batch_compact, whose post-condition holds word for
+ * word.  Flags and thresholds stay on the device until the end: only the per-pair counts and thresholds come back (and the
+ * kept row numbers, if asked for).  rank, scale, threshold, n_kept: [num_pairs].  Replaces sba_batch_residuals(sq_norm) +
+ * host partitions + sba_batch_compact with a host-built mask.                                                          */
+int sba_batch_keep_below(sba_batch* b, int depth_mode, const double* rot, const double* tran, const double* d1,
+                         const double* d2, const size_t* rank, const double* scale, double* threshold, size_t* n_kept,
+                         long long* kept_index);
 
 /* ---- callers / data formats either side of the path ------------------------------------- */
 /* pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298).  keypoints: n records of

@@ -105,6 +105,10 @@ SIGNATURES = {
     "sba_problem_residuals": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_double, C.c_double, C.c_double, _dp, _dp, _vp,
                                         C.POINTER(C.c_size_t)]),
     "sba_problem_compact": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t), _vp]),
+    "sba_problem_residual_order_stats": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_double, C.c_double, C.POINTER(C.c_size_t),
+                                                   C.c_int, _dp]),
+    "sba_problem_keep_below": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_double, C.c_double, C.c_size_t, C.c_double, _dp,
+                                         C.POINTER(C.c_size_t), _vp]),
     "sba_problem_eval": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double,
                                    C.c_double, C.POINTER(NormalEq)]),
     "sba_problem_eval_pack": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_double,
@@ -165,6 +169,9 @@ SIGNATURES = {
     "sba_batch_residuals": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _vp, C.POINTER(C.c_size_t)]),
     "sba_batch_compact": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t), _vp]),
     "sba_batch_keep_inliers": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.POINTER(C.c_size_t), _vp]),
+    "sba_batch_residual_order_stats": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_size_t), C.c_int, _dp]),
+    "sba_batch_keep_below": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_size_t), _dp, _dp, C.POINTER(C.c_size_t),
+                                       _vp]),
     "sba_batch_solve_problem": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp, C.POINTER(LmOptions), _vp, _dp,
                                           C.POINTER(C.c_int), C.POINTER(LmSummary), C.POINTER(LmSummary), C.POINTER(LmSummary),
                                           C.POINTER(C.c_int)]),

@@ -137,6 +137,24 @@ def _offsets(o, name):
     return off
 
 
+def quantile_rank(probs, n: int) -> np.ndarray:
+    """The 0-based rank floor(p * (n - 1)) of each probability 0 <= p <= 1 among n > 0 values, formed in float64: p = 0 is
+    the minimum, p = 1 the maximum, and no interpolation between neighbours takes place."""
+    p = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    if n < 1:
+        raise ValueError("quantiles of an empty set")
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("probabilities must lie in [0, 1]")
+    return np.floor(p * np.float64(n - 1)).astype(np.uintp)
+
+
+def _ranks(r) -> np.ndarray:
+    a = np.asarray(r)
+    if a.size and (not np.issubdtype(a.dtype, np.integer) or a.min() < 0):
+        raise ValueError("ranks must be non-negative integers")
+    return np.ascontiguousarray(np.atleast_1d(a), dtype=np.uintp)
+
+
 def device_count() -> int:
     lib = cabi.load_library()
     n = C.c_int(0)
@@ -378,6 +396,39 @@ class Problem:
         indices of the matches kept."""
         r = self.residuals(rot, tran, d1, d2, huber_delta, depth_mode, fields=("inlier",))
         return self.compact(r.inlier)
+
+    def residual_order_stats(self, rot, tran, ranks, d1=1.0, d2=1.0, depth_mode=DEPTH_UNIFORM) -> np.ndarray:
+        """The ranks[j]-th smallest (0-based) of the per-match squared residual norms at (rot, tran), selected on the device:
+        each value is, bit for bit, an element of ``residuals(...).sq_norm``; nothing is interpolated.  Up to 8 ranks per
+        call, each below `size`.  A NaN sorts above +inf."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        r = _ranks(ranks).reshape(-1)
+        vals = np.empty(r.shape[0])
+        cabi.check(self._lib, self._lib.sba_problem_residual_order_stats(
+            self._h, depth_mode, _dptr(rot), _dptr(tran), d1, d2, r.ctypes.data_as(C.POINTER(C.c_size_t)), r.shape[0],
+            _dptr(vals)))
+        return vals
+
+    def residual_quantiles(self, rot, tran, probs, d1=1.0, d2=1.0, depth_mode=DEPTH_UNIFORM) -> np.ndarray:
+        """residual_order_stats at the ranks floor(p * (n - 1)) of the probabilities 0 <= p <= 1 (`quantile_rank`): the
+        lower of the two neighbours where numpy's default quantile would interpolate."""
+        return self.residual_order_stats(rot, tran, quantile_rank(probs, self.size), d1, d2, depth_mode)
+
+    def keep_below(self, rot, tran, prob, scale, d1=1.0, d2=1.0, depth_mode=DEPTH_UNIFORM):
+        """Keep the matches with sq_norm <= scale * (the `prob` quantile of sq_norm, as residual_quantiles), selected,
+        flagged and compacted on the device; the handle then equals a fresh upload of the kept matches.  A NaN residual is
+        dropped.  Returns (original indices of the kept matches (np.int64), the threshold).
+        `scale` has no default on purpose: which multiple of which quantile separates outliers depends on the stage -- after
+        the joint solve a residual keeps one effective degree of freedom, before it three -- so the choice is the caller's."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        n = self.size
+        rank = int(quantile_rank(prob, n).reshape(-1)[0])
+        idx = np.empty(max(n, 1), dtype=np.int64)
+        kept, thr = C.c_size_t(0), C.c_double(0.0)
+        cabi.check(self._lib, self._lib.sba_problem_keep_below(
+            self._h, depth_mode, _dptr(rot), _dptr(tran), d1, d2, rank, float(scale), C.byref(thr), C.byref(kept),
+            idx.ctypes.data_as(C.c_void_p)))
+        return idx[:kept.value].copy(), thr.value
 
     # -- solve stage --------------------------------------------------------------------------------
     def solve(self, mode, rot, tran, d1=1.0, d2=1.0, depth_mode=DEPTH_UNIFORM, options: cabi.LmOptions | None = None):
@@ -749,6 +800,58 @@ class Batch:
                                                                nk.ctypes.data_as(C.POINTER(C.c_size_t)),
                                                                idx.ctypes.data_as(C.c_void_p)))
         return self._compacted(idx, nk)
+
+    def _pair_ranks(self, probs):
+        """(num_pairs, k) ranks floor(p * (n[g] - 1)) of every pair's own size (0 for an empty pair, which takes no part)."""
+        n = np.diff(self._offsets.astype(np.int64))
+        p = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        return np.stack([quantile_rank(p, int(m)) if m > 0 else np.zeros(p.shape[0], dtype=np.uintp) for m in n]) \
+            if self.num_pairs else np.zeros((0, p.shape[0]), dtype=np.uintp)
+
+    def residual_order_stats(self, rot, tran, ranks, d1=None, d2=None, depth_mode=DEPTH_UNIFORM) -> np.ndarray:
+        """Every pair's ranks[g][j]-th smallest (0-based) squared residual norm among its own rows at its own (rot, tran),
+        all pairs in the same launches; `ranks` (num_pairs, k), k <= 8, or (k,) for every pair alike.  Returns
+        (num_pairs, k): elements of ``residuals(...).sq_norm`` bit for bit, NaN for an empty pair."""
+        rot, rp = self._pp(rot, 3)
+        tran, tp = self._pp(tran, 3)
+        d1a, d1p = self._pp(d1, 1)
+        d2a, d2p = self._pp(d2, 1)
+        r = _ranks(ranks)
+        if r.ndim == 1:
+            r = np.ascontiguousarray(np.broadcast_to(r, (self.num_pairs, r.shape[0])))
+        if r.ndim != 2 or r.shape[0] != self.num_pairs:
+            raise ValueError(f"ranks has shape {r.shape}, the batch holds {self.num_pairs} pairs")
+        vals = np.full((max(self.num_pairs, 1), r.shape[1]), np.nan)
+        cabi.check(self._lib, self._lib.sba_batch_residual_order_stats(
+            self._h, depth_mode, rp, tp, d1p, d2p, r.ctypes.data_as(C.POINTER(C.c_size_t)), r.shape[1], _dptr(vals)))
+        return vals[:self.num_pairs]
+
+    def residual_quantiles(self, rot, tran, probs, d1=None, d2=None, depth_mode=DEPTH_UNIFORM) -> np.ndarray:
+        """residual_order_stats at every pair's own ranks floor(p * (n[g] - 1)) (`quantile_rank` of the pair's size)."""
+        return self.residual_order_stats(rot, tran, self._pair_ranks(probs), d1, d2, depth_mode)
+
+    def keep_below(self, rot, tran, prob, scale, d1=None, d2=None, depth_mode=DEPTH_UNIFORM):
+        """Every pair keeps its rows with sq_norm <= scale[g] * (its own `prob` quantile of sq_norm); thresholds and flags
+        stay on the device, then compact()'s layout.  `prob` and `scale`: a number or one per pair.  Returns (kept row
+        numbers, the new offsets, the per-pair thresholds (NaN for an empty pair)).  `scale` has no default on purpose: the
+        right multiple of the right quantile depends on the stage (see Problem.keep_below)."""
+        rot, rp = self._pp(rot, 3)
+        tran, tp = self._pp(tran, 3)
+        d1a, d1p = self._pp(d1, 1)
+        d2a, d2p = self._pp(d2, 1)
+        B = self.num_pairs
+        n = np.diff(self._offsets.astype(np.int64))
+        prob = np.broadcast_to(np.asarray(prob, dtype=np.float64), (B,))
+        rank = np.array([int(quantile_rank(prob[g], int(n[g]))[0]) if n[g] > 0 else 0 for g in range(B)] + [0] * (B == 0),
+                        dtype=np.uintp)
+        sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (max(B, 1),)))
+        thr = np.full(max(B, 1), np.nan)
+        idx = np.empty(max(self._rows(), 1), dtype=np.int64)
+        nk = np.zeros(max(B, 1), dtype=np.uintp)
+        cabi.check(self._lib, self._lib.sba_batch_keep_below(
+            self._h, depth_mode, rp, tp, d1p, d2p, rank.ctypes.data_as(C.POINTER(C.c_size_t)), _dptr(sc), _dptr(thr),
+            nk.ctypes.data_as(C.POINTER(C.c_size_t)), idx.ctypes.data_as(C.c_void_p)))
+        return (*self._compacted(idx, nk), thr[:B].copy())
 
     def solve(self, mode, rot, tran, d1=None, d2=None, depth_mode=DEPTH_UNIFORM, options: cabi.LmOptions | None = None):
         """Per-pair LM in lock-step.  Returns (rot (B,3), tran (B,3), [SolveSummary], status (B,))."""

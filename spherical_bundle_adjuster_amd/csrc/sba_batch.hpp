@@ -102,5 +102,33 @@ int layout_pairs(sba_batch* b, const size_t* offsets, int num_pairs, int store, 
 // allocated on first use; the batched joint solve shares the planes (the two stages never overlap).
 int ensure_depth_work(sba_batch* b);
 
+// sba_batch_select.cpp -- what the entry points that look at single matches share (sba_quantile.cpp).
+size_t batch_rows(const sba_batch* b);
+sba::Planes batch_planes(const sba_batch* b);
+// The residual kernel at (rot, tran, d1, d2): every pair's sweep state is built on the device from the same 80-byte record a
+// batched step reads, so the residuals carry the sweep's bits.  out.n_inlier: num_pairs device words, zeroed here.
+int residual_pass(sba_batch* b, int depth_mode, const double* rot, const double* tran, const double* d1, const double* d2,
+                  double huber_delta, int outputs, const sba::ResidualOut& out);
+// Device scratch of one compaction: keep bytes (whole tiles, zero beyond the rows) | tile counts | tile offsets | total |
+// kept rows per pair | inlier counts per pair (keep_inliers).
+struct CompactWork {
+  explicit CompactWork(const int* poison) : buf(poison) {}
+  sba::DeviceBuffer buf;
+  size_t rows = 0, ntiles = 0;
+  unsigned char* keep = nullptr;
+  unsigned int* tile_count = nullptr;
+  unsigned long long* tile_offset = nullptr;
+  unsigned long long* total = nullptr;
+  unsigned long long* pair_kept = nullptr;
+  unsigned long long* n_inlier = nullptr;
+};
+
+int alloc_work(sba_batch* b, size_t rows, CompactWork* w);
+// w.keep holds the rows' flags (queued on the stream): counts every pair's kept rows, lays the batch out afresh for them and
+// moves the kept rows over -- everything sba_batch_compact does after its keep bytes are on the device.
+int compact_rows(sba_batch* b, CompactWork& w, size_t* n_kept, long long* kept_index);
+// No rows at all: every pair keeps nothing, and the offsets become those of an upload of nothing.
+void compact_nothing(sba_batch* b, size_t* n_kept);
+
 }  // namespace batch
 }  // namespace sba

@@ -15,8 +15,11 @@ using sba::batch::check_batch_args;
   } while (0)
 
 namespace {
-
 size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
+}  // namespace
+
+namespace sba {
+namespace batch {
 
 size_t batch_rows(const sba_batch* b) { return b->offsets.back() - b->offsets.front(); }
 
@@ -38,20 +41,6 @@ int residual_pass(sba_batch* b, int depth_mode, const double* rot, const double*
                                           b->state_host_dev, huber_delta, b->num_pairs, b->bpp, out, b->stream));
   return SBA_OK;
 }
-
-// Device scratch of one compaction: keep bytes (whole tiles, zero beyond the rows) | tile counts | tile offsets | total |
-// kept rows per pair | inlier counts per pair (keep_inliers).
-struct CompactWork {
-  explicit CompactWork(const int* poison) : buf(poison) {}
-  sba::DeviceBuffer buf;
-  size_t rows = 0, ntiles = 0;
-  unsigned char* keep = nullptr;
-  unsigned int* tile_count = nullptr;
-  unsigned long long* tile_offset = nullptr;
-  unsigned long long* total = nullptr;
-  unsigned long long* pair_kept = nullptr;
-  unsigned long long* n_inlier = nullptr;
-};
 
 int alloc_work(sba_batch* b, size_t rows, CompactWork* w) {
   const size_t B = static_cast<size_t>(b->num_pairs);
@@ -151,7 +140,15 @@ void compact_nothing(sba_batch* b, size_t* n_kept) {
   b->offsets.assign(static_cast<size_t>(b->num_pairs) + 1, 0);
 }
 
-}  // namespace
+}  // namespace batch
+}  // namespace sba
+
+using sba::batch::CompactWork;
+using sba::batch::alloc_work;
+using sba::batch::batch_rows;
+using sba::batch::compact_nothing;
+using sba::batch::compact_rows;
+using sba::batch::residual_pass;
 
 extern "C" {
 

@@ -4,6 +4,7 @@
 //   sba_stages.cpp     d-only stage and 8-point initial guess entry points
 //   sba_select.cpp     per-match residuals and compaction of the matches
 //   sba_joint.cpp      joint solve (depths, rotation and translation together) entry points
+//   sba_quantile.cpp   order statistics of the per-match squared residual norms and the keep-rule built on them
 // Internal: nothing here is exported from the library.
 #pragma once
 #include <cstdlib>
@@ -199,6 +200,22 @@ int alloc_planes(sba_problem* p, size_t n, bool with_d12, int store);
 int ensure_folded(sba_problem* p);
 int sweep_planes(sba_problem* p, int depth_mode, sba::Planes* pl, int* kernel_depth);
 int check_args(const sba_problem* p, int mode, int depth_mode, const double* rot, const double* tran);
+
+// sba_select.cpp -- the compaction behind sba_problem_compact, for callers whose keep bytes are already on the device
+// (sba_quantile.cpp).  compact_alloc: the device scratch of one compaction of the handle's n > 0 matches, the keep bytes
+// zeroed beyond n (enqueued); the caller then queues the n keep bytes on the handle's stream.  compact_rows: everything
+// sba_problem_compact does after that.
+struct CompactWork {
+  explicit CompactWork(const int* poison) : buf(poison) {}
+  sba::DeviceBuffer buf;
+  size_t ntiles = 0;
+  unsigned char* keep = nullptr;
+  unsigned int* tile_count = nullptr;
+  unsigned long long* tile_offset = nullptr;
+  unsigned long long* total = nullptr;
+};
+int compact_alloc(sba_problem* p, CompactWork* w);
+int compact_rows(sba_problem* p, CompactWork& w, size_t* n_kept, long long* kept_index);
 
 // sba_transport.cpp
 int allreduce_pack(sba_problem* p);                                  // p->pack_dev (24 doubles), then hand-over to the host

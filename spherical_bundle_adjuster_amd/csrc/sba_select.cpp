@@ -87,24 +87,44 @@ int sba_problem_compact(sba_problem* p, const unsigned char* keep, size_t* n_kep
     return SBA_OK;
   }
 
-  // keep bytes (whole tiles, zero beyond n) | tile counts | tile offsets | total
+  sba::shim::CompactWork w(&p->poisoned);
+  int rc = sba::shim::compact_alloc(p, &w);
+  if (rc) return rc;
+  SBA_TRY_HIP(hipMemcpyAsync(w.keep, keep, n, hipMemcpyHostToDevice, p->stream));
+  return sba::shim::compact_rows(p, w, n_kept, kept_index);
+}
+
+}  // extern "C"
+
+namespace sba {
+namespace shim {
+
+// keep bytes (whole tiles, zero beyond n) | tile counts | tile offsets | total
+int compact_alloc(sba_problem* p, CompactWork* w) {
+  const size_t n = p->n;
   const size_t ntiles = (n + sba::kCompactTile - 1) / sba::kCompactTile;
   auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
   const size_t keep_bytes = ntiles * sba::kCompactTile;
   const size_t off_count = up(keep_bytes), off_offset = off_count + up(ntiles * sizeof(unsigned int));
   const size_t off_total = off_offset + up(ntiles * sizeof(unsigned long long));
-  sba::DeviceBuffer work(&p->poisoned);
-  SBA_TRY_HIP(work.alloc(off_total + 256));
-  unsigned char* keep_dev = work.as<unsigned char>();
-  unsigned int* tile_count = reinterpret_cast<unsigned int*>(work.as<char>() + off_count);
-  unsigned long long* tile_offset = reinterpret_cast<unsigned long long*>(work.as<char>() + off_offset);
-  unsigned long long* total_dev = reinterpret_cast<unsigned long long*>(work.as<char>() + off_total);
-  if (keep_bytes > n) SBA_TRY_HIP(hipMemsetAsync(keep_dev + n, 0, keep_bytes - n, p->stream));
-  SBA_TRY_HIP(hipMemcpyAsync(keep_dev, keep, n, hipMemcpyHostToDevice, p->stream));
-  SBA_TRY_HIP(sba::launch_compact_count(keep_dev, ntiles, tile_count, p->stream));
-  SBA_TRY_HIP(sba::launch_compact_scan(tile_count, ntiles, tile_offset, total_dev, p->stream));
+  SBA_TRY_HIP(w->buf.alloc(off_total + 256));
+  w->ntiles = ntiles;
+  w->keep = w->buf.as<unsigned char>();
+  w->tile_count = reinterpret_cast<unsigned int*>(w->buf.as<char>() + off_count);
+  w->tile_offset = reinterpret_cast<unsigned long long*>(w->buf.as<char>() + off_offset);
+  w->total = reinterpret_cast<unsigned long long*>(w->buf.as<char>() + off_total);
+  if (keep_bytes > n) SBA_TRY_HIP(hipMemsetAsync(w->keep + n, 0, keep_bytes - n, p->stream));
+  return SBA_OK;
+}
+
+int compact_rows(sba_problem* p, CompactWork& w, size_t* n_kept, long long* kept_index) {
+  const size_t n = p->n, ntiles = w.ntiles;
+  unsigned char* keep_dev = w.keep;
+  unsigned long long* tile_offset = w.tile_offset;
+  SBA_TRY_HIP(sba::launch_compact_count(keep_dev, ntiles, w.tile_count, p->stream));
+  SBA_TRY_HIP(sba::launch_compact_scan(w.tile_count, ntiles, tile_offset, w.total, p->stream));
   unsigned long long total = 0;
-  SBA_TRY_HIP(hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, p->stream));
+  SBA_TRY_HIP(hipMemcpyAsync(&total, w.total, sizeof(total), hipMemcpyDeviceToHost, p->stream));
   SBA_SELECT_SYNC(p, "compaction count");   // the one synchronous step: the new planes are sized by it
   const size_t m = static_cast<size_t>(total);
 
@@ -157,4 +177,5 @@ int sba_problem_compact(sba_problem* p, const unsigned char* keep, size_t* n_kep
   return SBA_OK;
 }
 
-}  // extern "C"
+}  // namespace shim
+}  // namespace sba

@@ -181,33 +181,60 @@ int spherical_bundle_adjuster::solve_problem(sba_lm_options& opt, std::vector<cv
                 s.seconds_eval * 1e3);
   };
 
-  // stage 1: d-only (.cpp:196-197) -- per-match bounded depth refinement, lambda = c = 1 (.cpp:1057-1058)
-  if (match_num > 0) {
-    rc = sba_problem_solve_depths(problem, init_rot, init_tran, 1.0, 1.0, &opt,
-                                  reinterpret_cast<double*>(init_d.data()), &res.depth_stage);
-    if (rc) return rc;
-    report("d-only", res.depth_stage);
-  }
-  // stages 2 and 3 use init_d[0][0] and init_d[1][0] for EVERY match (.cpp:941-942, :998-999)
-  const double d1 = match_num > 0 ? init_d[0][0] : 0.0;
-  const double d2 = match_num > 1 ? init_d[1][0] : d1;
+  auto run_stages = [&](int num) -> int {
+    // stage 1: d-only (.cpp:196-197) -- per-match bounded depth refinement, lambda = c = 1 (.cpp:1057-1058)
+    if (num > 0) {
+      rc = sba_problem_solve_depths(problem, init_rot, init_tran, 1.0, 1.0, &opt,
+                                    reinterpret_cast<double*>(init_d.data()), &res.depth_stage);
+      if (rc) return rc;
+      report("d-only", res.depth_stage);
+    }
+    // stages 2 and 3 use init_d[0][0] and init_d[1][0] for EVERY match (.cpp:941-942, :998-999)
+    const double d1 = num > 0 ? init_d[0][0] : 0.0;
+    const double d2 = num > 1 ? init_d[1][0] : d1;
 
-  rc = sba_problem_solve(problem, SBA_MODE_ROT, SBA_DEPTH_UNIFORM, init_rot, init_tran, d1, d2, &opt, &res.rot_stage);   // .cpp:202-203
-  if (rc) return rc;
-  report("rot-only", res.rot_stage);
-  rc = sba_problem_solve(problem, SBA_MODE_TRAN, SBA_DEPTH_UNIFORM, init_rot, init_tran, d1, d2, &opt, &res.tran_stage); // .cpp:208-209
-  if (rc) return rc;
-  report("tran-only", res.tran_stage);
-
-  // optional stage 4 (set_joint_refinement): depths, rotation and translation together, from the staged result.  The
-  // handle still holds the d-only stage's depths; the sphere parameterisation keeps |tran| at its current length.
-  res.joint_stage = sba_lm_summary{};
-  if (joint_refinement && match_num > 0) {
-    sba_lm_options jopt = opt;
-    jopt.tran_param = SBA_TRAN_SPHERE;
-    rc = sba_problem_solve_joint(problem, init_rot, init_tran, &jopt, &res.joint_stage, reinterpret_cast<double*>(init_d.data()));
+    rc = sba_problem_solve(problem, SBA_MODE_ROT, SBA_DEPTH_UNIFORM, init_rot, init_tran, d1, d2, &opt, &res.rot_stage);   // .cpp:202-203
     if (rc) return rc;
-    report("joint", res.joint_stage);
+    report("rot-only", res.rot_stage);
+    rc = sba_problem_solve(problem, SBA_MODE_TRAN, SBA_DEPTH_UNIFORM, init_rot, init_tran, d1, d2, &opt, &res.tran_stage); // .cpp:208-209
+    if (rc) return rc;
+    report("tran-only", res.tran_stage);
+
+    // optional stage 4 (set_joint_refinement): depths, rotation and translation together, from the staged result.  The
+    // handle still holds the d-only stage's depths; the sphere parameterisation keeps |tran| at its current length.
+    res.joint_stage = sba_lm_summary{};
+    if (joint_refinement && num > 0) {
+      sba_lm_options jopt = opt;
+      jopt.tran_param = SBA_TRAN_SPHERE;
+      rc = sba_problem_solve_joint(problem, init_rot, init_tran, &jopt, &res.joint_stage, reinterpret_cast<double*>(init_d.data()));
+      if (rc) return rc;
+      report("joint", res.joint_stage);
+    }
+    return SBA_OK;
+  };
+  rc = run_stages(match_num);
+  if (rc) return rc;
+
+  // optional (set_outlier_rejection): the matches whose squared residual norm at the pose and depths reached lies above
+  // scale * (its `quantile` order statistic) leave the handle -- selected, flagged and compacted on the device
+  // (sba_problem_keep_below) -- and the same stages run once more on the rest, from the pose reached.
+  res.kept_size = match_num;
+  res.reject_threshold = 0.0;
+  if (reject_quantile >= 0.0 && match_num > 0) {
+    const size_t rank = static_cast<size_t>(std::floor(reject_quantile * static_cast<double>(match_num - 1)));
+    std::vector<long long> kept_index(static_cast<size_t>(match_num));
+    size_t kept = 0;
+    rc = sba_problem_keep_below(problem, SBA_DEPTH_PER_MATCH, init_rot, init_tran, 1.0, 1.0, rank, reject_scale,
+                                &res.reject_threshold, &kept, kept_index.data());
+    if (rc) return rc;
+    resident_left = nullptr;   // the handle no longer holds every match of the caller's arrays
+    resident_n = -1;
+    for (size_t k = 0; k < kept; ++k) init_d[k] = init_d[static_cast<size_t>(kept_index[k])];
+    init_d.resize(kept);
+    res.kept_size = static_cast<int>(kept);
+    std::printf("outlier rejection: threshold %.6e, kept %zu / %d\n", res.reject_threshold, kept, match_num);
+    rc = run_stages(static_cast<int>(kept));
+    if (rc) return rc;
   }
 
   std::cout << "expected rotation vector " << expected_roll << ' ' << expected_pitch << ' ' << expected_yaw << ' ' << std::endl;

@@ -70,6 +70,12 @@ class spherical_bundle_adjuster {
   // pose of the rot / tran stages, |tran| pinned at its current length (SBA_TRAN_SPHERE: the problem's gauge) --
   // sba_problem_solve_joint.  The printed pose, the log row and the depth log then carry the refined values.
   void set_joint_refinement(bool on) { joint_refinement = on; }
+  // Outlier rejection after the last stage (default off; not in the reference).  The matches whose squared residual norm
+  // at the pose and depths reached exceeds scale * (the floor(quantile * (n - 1))-th smallest of those norms) are dropped
+  // on the device (sba_problem_keep_below), the same stages run once more on the rest from the pose reached, and one line
+  // reports the threshold and kept / total.  0 <= quantile <= 1, scale >= 0; a negative quantile switches it off.  There is
+  // no default pair: after the joint refinement a residual keeps one effective degree of freedom, before it three.
+  void set_outlier_rejection(double quantile, double scale) { reject_quantile = quantile <= 1.0 ? quantile : -1.0; reject_scale = scale; }
   // Everything after the matcher: pixel -> sphere, initial values, three-stage solve, log row.
   // Returns 0 or a negative SBA_ERR_* (message via sba_last_error()).
   int do_bundle_adjustment_from_matches(const std::vector<cv::KeyPoint>& left_key,
@@ -88,6 +94,8 @@ class spherical_bundle_adjuster {
     sba_lm_summary depth_stage{}, rot_stage{}, tran_stage{};
     sba_lm_summary joint_stage{};  // all zero unless set_joint_refinement(true)
     int guess_candidates = 0;     // valid rotation candidates of the 8-point consensus
+    int kept_size = 0;            // matches left after set_outlier_rejection (match_size when off)
+    double reject_threshold = 0;  // its cut on the squared residual norm (0 when off)
   };
   const result& last_result() const { return res; }
 
@@ -108,6 +116,7 @@ class spherical_bundle_adjuster {
   unsigned long long guess_seed = 0;
   guess_sampling_t guess_sampling = GUESS_AUTO;
   bool joint_refinement = false;
+  double reject_quantile = -1.0, reject_scale = 0.0;   // set_outlier_rejection; off while the quantile is negative
   const void* resident_left = nullptr;   // coordinates currently resident in `problem`
   int resident_n = -1;
   sba_problem* problem = nullptr;
