@@ -358,6 +358,33 @@ int sba_problem_eval_joint(sba_problem* p, const double rot[3], const double tra
 int sba_problem_solve_joint(sba_problem* p, double rot[3], double tran[3], const sba_lm_options* opt,
                             sba_lm_summary* summary, double* d12_out);
 
+/* Covariance of the joint problem at (rot, tran) and the handle's depths -- what ceres::Covariance gives a Ceres user --
+ * without a host Jacobian: the robustified problem (sqrt(rho')-scaled Jacobian, Ceres' apply_loss_function = true),
+ * undamped, in the tangent space of the gauge (dimension m = 5 with SBA_TRAN_SPHERE, 6 with SBA_TRAN_FREE).  With S the
+ * reduced camera system of sba_problem_eval_joint at radius = +inf, P the 6 x m projection of the gauge and U_i, W_i, s_i
+ * a match's scaled 2x2 depth block, its 2x6 coupling and its depth scaling:
+ *     cov            = P (P^T S P)^-1 P^T                                       6 x 6 over [rot | tran], rank m
+ *     depth_cov[3 i] = (var d1_i, var d2_i, cov(d1_i, d2_i))  of  s_i (U_i^-1 + U_i^-1 W_i cov W_i^T U_i^-1) s_i
+ * (the depth-camera cross blocks are not formed).  Unscaled: multiply by sigma^2 = 2 cost / dof for residuals of unknown
+ * variance.  Two streaming passes; depth_cov == NULL skips the second.
+ * Degenerate matches: det(U) / (U11 U22) is sin^2 of the angle between the rays R x1 and x2.  A match whose value is
+ * <= min_sin2_parallax (>= 0; negative or NaN: SBA_ERR_INVALID_ARG) or not finite is left out of the problem: it adds
+ * nothing to S, cost or sum_w, counts in n_degenerate, and its depth_cov row is (+inf, +inf, 0).
+ * opt == NULL: the defaults with tran_param = SBA_TRAN_SPHERE (huber_delta, jacobi_scaling and tran_param are read).
+ * Refusals: those of sba_problem_solve_joint.  SBA_ERR_NUMERIC -- the handle stays usable, nothing is written -- when
+ * n_used < m, S is not finite, or a pivot of the unit-diagonal projected S is not above m * DBL_EPSILON (a rank-deficient
+ * gauge or scene).  The handle's depths and planes are not touched: a later solve returns the bits it returns without
+ * this call.                                                                                                          */
+typedef struct sba_joint_cov {
+  double cov[36];              /* ambient [rot0..2 tran0..2], rank m */
+  double cost, sum_w;          /* over the used matches               */
+  long long n_used, n_degenerate;
+  int dim, dof;                /* m; n_used - m                       */
+} sba_joint_cov;
+int sba_problem_covariance_joint(sba_problem* p, const double rot[3], const double tran[3],
+                                 const sba_lm_options* opt, double min_sin2_parallax,
+                                 sba_joint_cov* out, double* depth_cov /* double[3n] or NULL */);
+
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other
  * ranks by any host channel, then every rank calls sba_problem_comm_init_rank.  After that

@@ -51,6 +51,11 @@ class JointEq(C.Structure):
                 ("cost", C.c_double), ("sum_w", C.c_double), ("n_outlier", C.c_double), ("gd_max", C.c_double)]
 
 
+class JointCov(C.Structure):
+    _fields_ = [("cov", C.c_double * 36), ("cost", C.c_double), ("sum_w", C.c_double), ("n_used", C.c_longlong),
+                ("n_degenerate", C.c_longlong), ("dim", C.c_int), ("dof", C.c_int)]
+
+
 class LmOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int),
                 ("initial_trust_region_radius", C.c_double),
@@ -126,6 +131,7 @@ SIGNATURES = {
                                            C.POINTER(LmSummary)]),
     "sba_problem_eval_joint": (C.c_int, [_vp, _dp, _dp, C.c_double, C.POINTER(LmOptions), C.POINTER(JointEq)]),
     "sba_problem_solve_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(LmSummary), _vp]),
+    "sba_problem_covariance_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(JointCov), _dp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

@@ -40,6 +40,25 @@ class JointEquations:
 
 
 @dataclass
+class JointCovariance:
+    """Covariance of the joint problem at a point (Problem.covariance_joint): the robustified, undamped problem in the
+    tangent space of the gauge.  Multiply by sigma2 for residuals of unknown variance."""
+    cov: np.ndarray                # (6, 6) over [rot | tran], rank dim
+    depth_cov: np.ndarray | None   # (n, 3) var d1, var d2, cov(d1, d2) per match; (inf, inf, 0) for a degenerate match
+    cost: float                    # over the used matches
+    sum_w: float
+    n_used: int
+    n_degenerate: int
+    dim: int                       # 5 with TRAN_SPHERE, 6 with TRAN_FREE
+    dof: int                       # n_used - dim
+
+    @property
+    def sigma2(self) -> float:
+        """2 cost / dof: the residual variance the fit itself suggests (nan without a degree of freedom)."""
+        return 2.0 * self.cost / self.dof if self.dof != 0 else float("nan")
+
+
+@dataclass
 class SolveSummary:
     termination: str
     num_iterations: int
@@ -476,6 +495,22 @@ class Problem:
                                                                 None if options is None else C.byref(options), C.byref(s),
                                                                 None if out is None else out.ctypes.data_as(C.c_void_p)))
         return rot, tran, out, _summary(s)
+
+    def covariance_joint(self, rot, tran, options: cabi.LmOptions | None = None, min_sin2_parallax: float = 0.0,
+                         depths: bool = True) -> JointCovariance:
+        """Covariance of the joint problem at (rot, tran) and the handle's depths: the pose's 6 x 6 block and (depths=True)
+        every match's own 2 x 2 depth block.  A match whose rays R x1 and x2 enclose an angle with sin^2 <=
+        min_sin2_parallax is left out and reported as (inf, inf, 0).  options None = the defaults with tran_param =
+        TRAN_SPHERE.  The handle's state is not touched."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        res = cabi.JointCov()
+        dd = np.zeros((self.size, 3)) if depths else None
+        cabi.check(self._lib, self._lib.sba_problem_covariance_joint(self._h, _dptr(rot), _dptr(tran),
+                                                                     None if options is None else C.byref(options),
+                                                                     float(min_sin2_parallax), C.byref(res),
+                                                                     None if dd is None else _dptr(dd)))
+        return JointCovariance(np.array(res.cov, dtype=np.float64).reshape(6, 6), dd, float(res.cost), float(res.sum_w),
+                               int(res.n_used), int(res.n_degenerate), int(res.dim), int(res.dof))
 
     # -- 8-point initial guess ----------------------------------------------------------------------
     def epipolar_moments(self) -> np.ndarray:

@@ -399,6 +399,15 @@ hipError_t launch_joint_step(int store, const Planes& pl, const double* d1, cons
                              const double* sc1, const double* sc2, const JointParams& prm, double* partials, int grid,
                              double* out, double* host_out, unsigned long long seq, hipStream_t stream);
 
+// Covariance of the joint solve (sba_covariance.hip; algebra and host finish: sba_covariance.hpp).  prm: a first reduce
+// pass's JointParams with inv_radius = 0.  Reduce: partials [grid][COV_ROW], out (device) the COV_OUT_* slots.  Depth:
+// sigma_c the ambient 6 x 6 camera covariance, out [(n + 1) / 2][6] doubles = (var d1, var d2, cov) per match.
+hipError_t cov_blocks_per_cu(int store, int* blocks);   // resident 256-thread blocks per CU of cov_reduce_kernel
+hipError_t launch_cov_reduce(int store, const Planes& pl, const double* d1, const double* d2, const JointParams& prm,
+                             double min_sin2, double* partials, int grid, double* out, hipStream_t stream);
+hipError_t launch_cov_depth(int store, const Planes& pl, const double* d1, const double* d2, const JointParams& prm,
+                            double min_sin2, const double sigma_c[36], double* out, int grid, hipStream_t stream);
+
 // Batched joint solve (sba_batch_joint.hip): ONE 256-thread block per pair -- the reduce body's ~350 registers fit one wave per
 // SIMD only, a 512-thread block would halve the budget and spill into the hot loop.  BatchJointPass: what the lock-step driver
 // hands over per pair and pass (mapped pinned host memory): the pass kind (kJointReduce / kJointStep), the current camera, for a

@@ -4,6 +4,7 @@
 //   sba_stages.cpp     d-only stage and 8-point initial guess entry points
 //   sba_select.cpp     per-match residuals and compaction of the matches
 //   sba_joint.cpp      joint solve (depths, rotation and translation together) entry points
+//   sba_covariance.cpp covariance of the joint solve at a point (pose 6x6, per-match depth blocks)
 //   sba_quantile.cpp   order statistics of the per-match squared residual norms and the keep-rule built on them
 // Internal: nothing here is exported from the library.
 #pragma once
@@ -40,6 +41,7 @@ struct sba_problem {
   double* joint_host_dev = nullptr;  // sequence word); allocated by the first joint call.  Its device planes share depth_scratch
   unsigned long long joint_seq = 0;
   int joint_occ[2] = {0, 0};       // resident blocks per CU of joint_reduce_kernel per [store]
+  int cov_occ[2] = {0, 0};         // ... and of cov_reduce_kernel (sba_covariance.cpp; its rows and outputs share depth_scratch)
   void* subset_scratch = nullptr;  // reference sampling: [trials][45] moments, then the [trials][m] index lists; kept across calls
   size_t subset_scratch_bytes = 0;
   void* select_scratch = nullptr;  // per-match residuals: inlier count, then the requested outputs; kept across calls

@@ -209,6 +209,24 @@ int spherical_bundle_adjuster::solve_problem(sba_lm_options& opt, std::vector<cv
       rc = sba_problem_solve_joint(problem, init_rot, init_tran, &jopt, &res.joint_stage, reinterpret_cast<double*>(init_d.data()));
       if (rc) return rc;
       report("joint", res.joint_stage);
+      // optional (set_joint_covariance): how far to trust that pose -- the joint problem's covariance at it, scaled by the
+      // residual variance the fit suggests.  A rank-deficient scene has none: that is reported, not an error of the run.
+      if (joint_covariance) {
+        sba_joint_cov cov;
+        rc = sba_problem_covariance_joint(problem, init_rot, init_tran, &jopt, 0.0, &cov, nullptr);
+        if (rc == SBA_ERR_NUMERIC) {
+          std::printf("joint covariance: none (%s)\n", sba_last_error());
+        } else if (rc) {
+          return rc;
+        } else {
+          const double s2 = cov.dof > 0 ? 2.0 * cov.cost / cov.dof : 0.0;
+          double sd[6];
+          for (int a = 0; a < 6; ++a) sd[a] = std::sqrt(s2 * cov.cov[7 * a]);
+          std::printf("joint covariance: 1-sigma rot (deg) %.6e %.6e %.6e, tran %.6e %.6e %.6e (sigma^2 = 2 cost / dof = %.6e, "
+                      "%lld used, %lld degenerate)\n", sd[0] / kPi * 180.0, sd[1] / kPi * 180.0, sd[2] / kPi * 180.0, sd[3], sd[4], sd[5],
+                      s2, cov.n_used, cov.n_degenerate);
+        }
+      }
     }
     return SBA_OK;
   };

@@ -70,6 +70,9 @@ class spherical_bundle_adjuster {
   // pose of the rot / tran stages, |tran| pinned at its current length (SBA_TRAN_SPHERE: the problem's gauge) --
   // sba_problem_solve_joint.  The printed pose, the log row and the depth log then carry the refined values.
   void set_joint_refinement(bool on) { joint_refinement = on; }
+  // With the joint refinement on: one more line after the joint stage, the 1-sigma of rot (degrees) and tran from
+  // sba_problem_covariance_joint at the refined pose, scaled by 2 cost / dof.  Nothing else changes.
+  void set_joint_covariance(bool on) { joint_covariance = on; }
   // Outlier rejection after the last stage (default off; not in the reference).  The matches whose squared residual norm
   // at the pose and depths reached exceeds scale * (the floor(quantile * (n - 1))-th smallest of those norms) are dropped
   // on the device (sba_problem_keep_below), the same stages run once more on the rest from the pose reached, and one line
@@ -116,6 +119,7 @@ class spherical_bundle_adjuster {
   unsigned long long guess_seed = 0;
   guess_sampling_t guess_sampling = GUESS_AUTO;
   bool joint_refinement = false;
+  bool joint_covariance = false;
   double reject_quantile = -1.0, reject_scale = 0.0;   // set_outlier_rejection; off while the quantile is negative
   const void* resident_left = nullptr;   // coordinates currently resident in `problem`
   int resident_n = -1;
