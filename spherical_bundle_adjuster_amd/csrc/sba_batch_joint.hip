@@ -1,7 +1,8 @@
 // Batched joint solve on the device: every pair's depths, rotation and translation free together (the reference's
 // ba_spherical_costfunctor, spherical_bundle_adjuster.cpp:843-889, once per pair of a batch).  The passes are those of
-// sba_joint.hip: its per-match block and fold, and its two per-match loops in their form over a pair layout (sba_joint_core.hpp;
-// sba_joint.hip keeps its own written-out copy of the loops, see there), run by ONE 256-thread block per pair:
+// sba_joint.hip: its per-match block and fold, and its two per-match loops (sba_joint_reduce_loop.inc / sba_joint_step_loop.inc,
+// the one text both files compile) as joint_reduce_stream / joint_step_stream over a pair layout (sba_joint_core.hpp), run by
+// ONE 256-thread block per pair:
 //   batch_joint_pass_kernel   one pass (reduce or step) of every pair that takes part, from a per-pair record; the pair's row is
 //                             published to mapped host memory, the last block stores the sequence word the host polls
 //                             (sba_batch_eval_joint and the lock-step driver of sba_batch_solve_joint)

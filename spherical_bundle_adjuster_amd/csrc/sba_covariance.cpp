@@ -53,9 +53,7 @@ int sba_problem_covariance_joint(sba_problem* p, const double rot[3], const doub
     SBA_TRY_HIP(sba::cov_blocks_per_cu(p->store, &occ));
     occ = std::max(1, occ);
   }
-  int cap = 8;   // SBA_JOINT_BLOCKS_PER_CU, as the joint solve's passes (tests force long grid-stride loops)
-  if (const char* env = std::getenv("SBA_JOINT_BLOCKS_PER_CU")) { const int v = std::atoi(env); if (v >= 1 && v <= 16) cap = v; }
-  const int grid = static_cast<int>(std::min<size_t>((npairs + 255) / 256, static_cast<size_t>(p->num_cus) * std::max(1, std::min(occ, cap))));
+  const int grid = sba::joint_grid(npairs, p->num_cus, occ);
 
   sba::Planes pl;
   for (int k = 0; k < 3; ++k) { pl.x1[k] = p->coord[k]; pl.x2[k] = p->coord[3 + k]; }

@@ -2,8 +2,10 @@
 // (sba_kernels.hip, sba_batch_kernels.hip, sba_side.hip, sba_depth.hip, sba_epipolar.hip).  Nothing here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 
 #include "../../include/sba_hip.h"
 #include "sba_depth_solver.hpp"
@@ -392,6 +394,14 @@ struct JointParams {
 // Results: the JOINT_OUT_* / JOINT_STEP_* slots (sba_joint_solver.hpp) in out (device) and, with host_out (mapped host
 // memory, JOINT_ROW + 1 words), published there followed by `seq` at host_out[JOINT_ROW].  partials: [grid][JOINT_ROW].
 hipError_t joint_blocks_per_cu(int store, int* blocks);   // resident 256-thread blocks per CU of joint_reduce_kernel
+// Grid of a grid-stride pass over npairs 16-byte vectors (256 per block) by a kernel of occupancy occ: at most
+// SBA_JOINT_BLOCKS_PER_CU (1 .. 16, default 8) resident blocks per CU -- fewer than the occupancy where tests force long
+// grid-stride loops -- and no block without a vector.  The joint solve's passes and its covariance share it.
+inline int joint_grid(size_t npairs, int num_cus, int occ) {
+  int cap = 8;
+  if (const char* env = std::getenv("SBA_JOINT_BLOCKS_PER_CU")) { const int v = std::atoi(env); if (v >= 1 && v <= 16) cap = v; }
+  return static_cast<int>(std::min<size_t>((npairs + 255) / 256, static_cast<size_t>(num_cus) * std::max(1, std::min(occ, cap))));
+}
 hipError_t launch_joint_reduce(int store, const Planes& pl, const double* d1, const double* d2, double* sc1, double* sc2,
                                const JointParams& prm, double* partials, int grid, double* out, double* host_out,
                                unsigned long long seq, hipStream_t stream);

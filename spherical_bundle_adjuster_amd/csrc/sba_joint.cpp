@@ -66,9 +66,7 @@ int joint_prepare(sba_problem* p, JointWork* w) {
     SBA_TRY_HIP(sba::joint_blocks_per_cu(p->store, &occ));
     occ = std::max(1, occ);
   }
-  int cap = 8;   // SBA_JOINT_BLOCKS_PER_CU: fewer resident blocks per CU than the kernel's occupancy (tests force long grid-stride loops)
-  if (const char* env = std::getenv("SBA_JOINT_BLOCKS_PER_CU")) { const int v = std::atoi(env); if (v >= 1 && v <= 16) cap = v; }
-  w->grid = static_cast<int>(std::min<size_t>(((n + 1) / 2 + 255) / 256, static_cast<size_t>(p->num_cus) * std::max(1, std::min(occ, cap))));
+  w->grid = sba::joint_grid((n + 1) / 2, p->num_cus, occ);
   for (int k = 0; k < 3; ++k) { w->pl.x1[k] = p->coord[k]; w->pl.x2[k] = p->coord[3 + k]; }
   w->pl.d1 = p->dplane[0]; w->pl.d2 = p->dplane[1];
   return SBA_OK;

@@ -24,12 +24,13 @@ namespace sba {
 namespace {
 
 // The per-match block (JointBlock / joint_block), the plane accesses (JPair, JointRegs) and the block fold come from
-// sba_joint_core.hpp, which the batched kernels (sba_batch_joint.hip) share.  The two loops below are ALSO in that header, as
-// joint_reduce_stream / joint_step_stream over an address map, and the batched kernels use them from there.  These kernels
-// keep their loops written out: routed through the stream functions the same lines compile to the same instruction counts
-// but other last bits (which product of a sum is contracted into an FMA depends on the order the compiler meets them in) --
-// S of a 4 097-match case moved from 2e-13 to 5e-12 off the long-double reference.  As they stand these three kernels are,
-// instruction for instruction, the ones from before the header was split off.
+// sba_joint_core.hpp, which the batched kernels (sba_batch_joint.hip) share.  The two per-match loops are written once, in
+// sba_joint_reduce_loop.inc / sba_joint_step_loop.inc.  The kernels below expand those files in their own bodies (over the
+// identity map); the batched kernels get them through the header's joint_reduce_stream / joint_step_stream.  A call of the
+// stream functions here would not do: a function is unrolled and simplified on its own before it is inlined, the kernel then
+// takes its parameters apart in another order, and the same lines come out with the same instruction counts but other last
+// bits -- S of a 4 097-match case moved from 2e-13 to 5e-12 off the long-double reference.  Expanded in
+// place, the kernels are instruction for instruction the ones from before the header was split off.
 
 // Pass 1.  ONE resident block per CU (one wave per SIMD): the 52 accumulators (104 registers), the register double buffer
 // (80) and a match's temporaries need ~350 registers; held to 256 (two blocks per CU) the kernel spills 340-396 B of
@@ -45,69 +46,8 @@ __global__ __launch_bounds__(256, 1) void joint_reduce_kernel(Planes pl, const d
   double acc[JOINT_OUT_COUNT];
 #pragma unroll
   for (int k = 0; k < JOINT_OUT_COUNT; ++k) acc[k] = 0.0;
-  JointRegs<ST> cur, nxt;
-  if (pr < npairs) cur.load(pl, d1, d2, sc1, sc2, load_scale, pr);
-  while (pr < npairs) {
-    const size_t pn = pr + stride;
-    if (pn < npairs) nxt.load(pl, d1, d2, sc1, sc2, load_scale, pn);
-    double NS1[2], NS2[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const bool valid = 2 * pr + h < n;
-      JointBlock b;
-      joint_block(P, cur.X[h], cur.Y[h], cur.Z[h], cur.U[h], cur.V[h], cur.W[h], cur.A[h], cur.B[h], cur.S1[h], cur.S2[h], valid, b);
-      NS1[h] = b.s1; NS2[h] = b.s2;
-      const double w = b.w;
-      // unreduced camera block, SBA_PACK_* layout (as the explicit sweep kernel accumulates it)
-      double wA[3][3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) wA[r][j] = w * b.A[r][j];
-      double ff[21], fe[6];      // w F^T F (upper, row by row) and w F^T e of this match
-      int k = 0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int c = a; c < 3; ++c) ff[k++] = wA[0][a] * b.A[0][c] + wA[1][a] * b.A[1][c] + wA[2][a] * b.A[2][c];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) ff[k++] = wA[c][a];
-        fe[a] = wA[0][a] * b.e[0] + wA[1][a] * b.e[1] + wA[2][a] * b.e[2];
-      }
-      ff[15] = w; ff[16] = 0.0; ff[17] = 0.0; ff[18] = w; ff[19] = 0.0; ff[20] = w;
-      fe[3] = w * b.e[0]; fe[4] = w * b.e[1]; fe[5] = w * b.e[2];
-      // pack slots: HAA = ff[0..2], ff[6..7], ff[11]; HAT[3 a + c] = ff rows a, columns 3..5
-      acc[0] += ff[0]; acc[1] += ff[1]; acc[2] += ff[2]; acc[3] += ff[6]; acc[4] += ff[7]; acc[5] += ff[11];
-      acc[6] += ff[3]; acc[7] += ff[4]; acc[8] += ff[5]; acc[9] += ff[8]; acc[10] += ff[9]; acc[11] += ff[10];
-      acc[12] += ff[12]; acc[13] += ff[13]; acc[14] += ff[14];
-      acc[SBA_PACK_SW] += w;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) acc[SBA_PACK_GA + a] += fe[a];          // GA[3], GT[3] are consecutive slots
-      acc[SBA_PACK_COST] = __builtin_fma(0.5, b.rho, acc[SBA_PACK_COST]);
-      acc[SBA_PACK_NOUT] += b.is_out;
-      // Schur complement of the depth block: z = U^-1 W (two rows), T = W^T z
-      double z1[6], z2[6];
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        z1[a] = (b.U22 * b.w1[a] - b.U12 * b.w2[a]) * b.inv_det;
-        z2[a] = (b.U11 * b.w2[a] - b.U12 * b.w1[a]) * b.inv_det;
-      }
-      k = 0;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-#pragma unroll
-        for (int c = a; c < 6; ++c) {
-          acc[JOINT_OUT_S + k] += ff[k] - (b.w1[a] * z1[c] + b.w2[a] * z2[c]);
-          ++k;
-        }
-        acc[JOINT_OUT_GS + a] += fe[a] - (z1[a] * b.G1 + z2[a] * b.G2);
-      }
-      if (valid) acc[JOINT_OUT_GDMAX] = fmax(acc[JOINT_OUT_GDMAX], fmax(fabs(b.gd1), fabs(b.gd2)));
-    }
-    if (P.first) { joint_store_pair(sc1, pr, NS1[0], NS1[1]); joint_store_pair(sc2, pr, NS2[0], NS2[1]); }
-    cur = nxt;
-    pr = pn;
-  }
+  const IdentityMap map;
+#include "sba_joint_reduce_loop.inc"
   joint_block_fold<JOINT_OUT_COUNT, JOINT_OUT_GDMAX>(acc, red, partials + static_cast<size_t>(blockIdx.x) * JOINT_ROW);
 }
 
@@ -121,51 +61,8 @@ __global__ __launch_bounds__(256, 2) void joint_step_kernel(Planes pl, const dou
   const size_t n = P.cur.n, npairs = (n + 1) / 2, stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   size_t pr = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   double acc[JOINT_STEP_COUNT] = {0.0, 0.0, 0.0, 0.0};
-  JointRegs<ST> cur, nxt;
-  if (pr < npairs) cur.load(pl, d1, d2, sc1, sc2, true, pr);
-  while (pr < npairs) {
-    const size_t pn = pr + stride;
-    if (pn < npairs) nxt.load(pl, d1, d2, sc1, sc2, true, pn);
-    double NA[2], NB[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const bool valid = 2 * pr + h < n;
-      const double x = cur.X[h], y = cur.Y[h], z = cur.Z[h], u = cur.U[h], v = cur.V[h], q = cur.W[h];
-      const double a = cur.A[h], bd = cur.B[h];
-      JointBlock b;
-      joint_block(P, x, y, z, u, v, q, a, bd, cur.S1[h], cur.S2[h], valid, b);
-      // delta d = -U^-1 (g_d + W delta c), in scaled coordinates, then unscaled
-      double t1 = b.G1, t2 = b.G2;
-#pragma unroll
-      for (int k = 0; k < 6; ++k) { t1 += b.w1[k] * P.delta_c[k]; t2 += b.w2[k] * P.delta_c[k]; }
-      const double y1 = (b.U12 * t2 - b.U22 * t1) * b.inv_det, y2 = (b.U12 * t1 - b.U11 * t2) * b.inv_det;
-      const double dl1 = b.s1 * y1, dl2 = b.s2 * y2;
-      const double na = a + dl1, nb = bd + dl2;
-      NA[h] = valid ? na : 0.0; NB[h] = valid ? nb : 0.0;     // the padding stays zero
-      // J delta = E delta d + A delta w + delta t
-      double jd[3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-        jd[r] = b.nu[r] * dl1 + (r == 0 ? u : (r == 1 ? v : q)) * dl2 + b.A[r][0] * P.delta_c[0] + b.A[r][1] * P.delta_c[1] +
-                b.A[r][2] * P.delta_c[2] + P.delta_c[3 + r];
-      // the residual at the candidate (w', t', d'), formed as every residual of the library
-      double X = x, Y = y, Z = z, Uc = u, Vc = v, Qc = q, r0, r1, r2, f0, f1, f2;
-      residual<DEPTH_PER_MATCH>(&P.cand, X, Y, Z, Uc, Vc, Qc, na, nb, r0, r1, r2, f0, f1, f2);
-      const double sc = sq_norm(f0, f1, f2);
-      double wc = 1.0, rhoc = sc, outc = 0.0;
-      if (P.cur.delta > 0.0) huber(sc, P.cur.delta, P.cur.delta2, wc, rhoc, outc);
-      if (valid) {
-        acc[JOINT_STEP_CAND_COST] = __builtin_fma(0.5, rhoc, acc[JOINT_STEP_CAND_COST]);
-        acc[JOINT_STEP_MODEL] -= b.w * (jd[0] * (b.e[0] + 0.5 * jd[0]) + jd[1] * (b.e[1] + 0.5 * jd[1]) + jd[2] * (b.e[2] + 0.5 * jd[2]));
-        acc[JOINT_STEP_DSTEP2] += dl1 * dl1 + dl2 * dl2;
-        acc[JOINT_STEP_D2] += a * a + bd * bd;
-      }
-    }
-    joint_store_pair(c1, pr, NA[0], NA[1]);
-    joint_store_pair(c2, pr, NB[0], NB[1]);
-    cur = nxt;
-    pr = pn;
-  }
+  const IdentityMap map;
+#include "sba_joint_step_loop.inc"
   joint_block_fold<JOINT_STEP_COUNT, -1>(acc, red, partials + static_cast<size_t>(blockIdx.x) * JOINT_ROW);
 }
 
