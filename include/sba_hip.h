@@ -592,6 +592,29 @@ int sba_batch_eval_joint(sba_batch* b, const double* rot, const double* tran, do
 int sba_batch_solve_joint(sba_batch* b, double* rot, double* tran, const sba_lm_options* opt, sba_lm_summary* summaries,
                           int* status, double* d12_out);
 
+/* sba_batch_covariance_joint: the covariance of the joint problem (sba_problem_covariance_joint) for EVERY pair of the batch.
+ * Pair g gets what sba_problem_covariance_joint computes on pair g alone at (rot[g], tran[g]) and the batch's resident depths,
+ * up to the summation order: the same robustified, undamped problem, gauge projection, degeneracy rule and (+inf, +inf, 0) rows.
+ * out: sba_joint_cov[num_pairs]; depth_cov (may be NULL: no depth phase): double[offsets[num_pairs]][3], indexed like the
+ * uploaded d12 and like d12_out of sba_batch_solve_joint (pair g's match i at row offsets[g] + i, which is row
+ * offsets[g] - offsets[0] + i of the batch's own rows); status (may be NULL): int[num_pairs].
+ * opt == NULL: the defaults with tran_param = SBA_TRAN_SPHERE.
+ * Whole-call refusals, decided before a device is touched: those of sba_batch_solve_joint; out == NULL with pairs present,
+ * or min_sin2_parallax negative or NaN: SBA_ERR_INVALID_ARG.
+ * Per pair -- the contract of sba_batch_solve_joint: a pair whose rot / tran is not finite, whose n_used < m (an empty pair
+ * included), whose S is not finite or whose unit-diagonal projected S has a pivot not above m * DBL_EPSILON FAILS:
+ * status[g] = SBA_ERR_NUMERIC, out[g].cov all NaN and its depth_cov rows NaN (not zero: a zero covariance reads as
+ * certainty); cost, sum_w, n_used, n_degenerate are those of its reduce pass, dim = m, dof = n_used - m.  The call returns
+ * SBA_ERR_NUMERIC when any pair failed; the other pairs' results are valid and the handle stays usable.
+ * The batch is not touched (depth planes, scaling state, layout): a later solve, residuals or compaction returns the bits it
+ * returns without this call.  One 256-thread block per pair runs the pair's whole covariance -- reduce pass, finish, depth pass
+ * -- in one launch; the per-match array comes back in one copy.  A pair's sums depend on its own matches only: its results are
+ * the same bits alone in a batch, among other pairs, and in either pair layout.  SBA_BATCH_DEVICE_COV=0: a reduce launch, the
+ * finish on the host, a depth launch -- the two drivers agree to the bit.                                                     */
+int sba_batch_covariance_joint(sba_batch* b, const double* rot, const double* tran, const sba_lm_options* opt,
+                               double min_sin2_parallax, sba_joint_cov* out /* [num_pairs] */,
+                               double* depth_cov /* double[offsets[num_pairs]][3] or NULL */, int* status /* [num_pairs] or NULL */);
+
 /* ---- single matches of a batch: residuals, inlier sets, compaction ---- */
 /* Rows r = 0 .. total - 1 with total = offsets[num_pairs] - offsets[0] of the current layout; row r is the caller's row
  * offsets[0] + r.  rot, tran, d1, d2 as for sba_batch_eval (per pair; NULL depths mean 1.0; ignored with

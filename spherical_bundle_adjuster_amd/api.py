@@ -59,6 +59,37 @@ class JointCovariance:
 
 
 @dataclass
+class BatchJointCovariance:
+    """Covariance of every pair's joint problem (Batch.covariance_joint).  A pair with status != 0 has no covariance: its cov
+    and its depth_cov rows are NaN.  Multiply a pair's blocks by its sigma2 for residuals of unknown variance."""
+    cov: np.ndarray                # (B, 6, 6) over [rot | tran], rank dim
+    depth_cov: np.ndarray | None   # (offsets[-1], 3) indexed like the uploaded d12; (inf, inf, 0) for a degenerate match
+    cost: np.ndarray               # (B,) over the used matches
+    sum_w: np.ndarray              # (B,)
+    n_used: np.ndarray             # (B,) int64
+    n_degenerate: np.ndarray       # (B,) int64
+    dim: np.ndarray                # (B,) int32
+    dof: np.ndarray                # (B,) int32: n_used - dim
+    status: np.ndarray             # (B,) int32: 0 or SBA_ERR_NUMERIC
+    offsets: np.ndarray            # (B + 1,) first depth_cov row of every pair
+
+    @property
+    def sigma2(self) -> np.ndarray:
+        """(B,) 2 cost / dof per pair (nan without a degree of freedom)."""
+        dof = np.asarray(self.dof, dtype=np.float64)
+        out = np.full(dof.shape, np.nan)
+        np.divide(2.0 * np.asarray(self.cost, dtype=np.float64), dof, out=out, where=dof != 0)
+        return out
+
+    def pair(self, g: int) -> JointCovariance:
+        """Pair g's slice as the single-problem result type."""
+        g = int(g)
+        lo, hi = int(self.offsets[g]), int(self.offsets[g + 1])
+        return JointCovariance(self.cov[g], None if self.depth_cov is None else self.depth_cov[lo:hi], float(self.cost[g]),
+                               float(self.sum_w[g]), int(self.n_used[g]), int(self.n_degenerate[g]), int(self.dim[g]), int(self.dof[g]))
+
+
+@dataclass
 class SolveSummary:
     termination: str
     num_iterations: int
@@ -948,6 +979,31 @@ class Batch:
         if check or rc != cabi.SBA_ERR_NUMERIC:
             cabi.check(self._lib, rc)
         return rot, tran, d12, [_summary(sums[i]) for i in range(B)], status[:B]
+
+    def covariance_joint(self, rot, tran, options: cabi.LmOptions | None = None, min_sin2_parallax: float = 0.0,
+                         depths: bool = True, check: bool = True) -> BatchJointCovariance:
+        """Covariance of every pair's joint problem at (rot[g], tran[g]) and the batch's depths, in one launch: per pair what
+        Problem.covariance_joint gives on that pair alone.  depths=False skips the per-match blocks.  options None = the
+        defaults with tran_param = TRAN_SPHERE.  A pair without a covariance (non-finite point, too few used matches, a
+        rank-deficient system) has status SBA_ERR_NUMERIC and NaN blocks; check=True raises SbaError then, check=False returns
+        the result with status, as solve_joint does.  The batch's state is not touched."""
+        B = self.num_pairs
+        rot = _f64(rot).reshape(B, 3)
+        tran = _f64(tran).reshape(B, 3)
+        res = (cabi.JointCov * max(B, 1))()
+        dd = np.zeros((int(self._total), 3)) if depths else None
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        rc = self._lib.sba_batch_covariance_joint(self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options),
+                                                  float(min_sin2_parallax), res, None if dd is None else _dptr(dd),
+                                                  status.ctypes.data_as(C.POINTER(C.c_int)))
+        if check or rc != cabi.SBA_ERR_NUMERIC:
+            cabi.check(self._lib, rc)
+        r = res[:B]
+        return BatchJointCovariance(np.array([list(e.cov) for e in r], dtype=np.float64).reshape(B, 6, 6), dd,
+                                    np.array([e.cost for e in r], dtype=np.float64), np.array([e.sum_w for e in r], dtype=np.float64),
+                                    np.array([e.n_used for e in r], dtype=np.int64), np.array([e.n_degenerate for e in r], dtype=np.int64),
+                                    np.array([e.dim for e in r], dtype=np.int32), np.array([e.dof for e in r], dtype=np.int32),
+                                    status[:B].copy(), np.asarray(self.offsets, dtype=np.int64).copy())
 
     def solve_problem(self, rot=None, tran=None, use_initial_guess: bool = True, trials: int = 80, subset_fraction: float = 0.25,
                       seed: int = 0, options: cabi.LmOptions | None = None, want_depths: bool = False, check: bool = True,

@@ -43,6 +43,8 @@ int free_batch_data(sba_batch* b) {
   if (b->joint_pass_host) SBA_TRY_HIP(hipHostFree(b->joint_pass_host));
   if (b->joint_out_host) SBA_TRY_HIP(hipHostFree(b->joint_out_host));
   b->joint_pass_host = nullptr; b->joint_pass_host_dev = nullptr; b->joint_out_host = nullptr; b->joint_out_host_dev = nullptr; b->joint_seq = 0;
+  if (b->cov_rec_host) SBA_TRY_HIP(hipHostFree(b->cov_rec_host));
+  b->cov_rec_host = nullptr; b->cov_rec_host_dev = nullptr; b->cov_seq = 0;
   if (b->epi_groups_dev) SBA_TRY_HIP(hipFree(b->epi_groups_dev));
   if (b->epi_groups_host) SBA_TRY_HIP(hipHostFree(b->epi_groups_host));
   if (b->offsets_dev) SBA_TRY_HIP(hipFree(b->offsets_dev));

@@ -57,6 +57,10 @@ struct sba_batch {
   double* joint_out_host = nullptr;           // pinned + mapped: [num_pairs][JOINT_ROW] rows, then the sequence word
   double* joint_out_host_dev = nullptr;
   unsigned long long joint_seq = 0;
+  // batched joint covariance (allocated on first use; its per-match output passes through depth_work)
+  sba::BatchCovRec* cov_rec_host = nullptr;           // pinned + mapped: [num_pairs] records, then the sequence word
+  sba::BatchCovRec* cov_rec_host_dev = nullptr;
+  unsigned long long cov_seq = 0;
   // batched initial guess (allocated on first use): the 64 x 45 group moments of every pair
   double* epi_groups_dev = nullptr;
   double* epi_groups_host = nullptr;          // pinned
@@ -101,6 +105,11 @@ int layout_pairs(sba_batch* b, const size_t* offsets, int num_pairs, int store, 
 // The work planes (candidate depths, depth Jacobi scaling: zeroed once) and the per-pair buffers of the batched d-only stage,
 // allocated on first use; the batched joint solve shares the planes (the two stages never overlap).
 int ensure_depth_work(sba_batch* b);
+
+// sba_batch_joint.cpp -- the whole-call refusals and the default options (the sphere gauge) of the batched joint entry
+// points, which the batched joint covariance shares (sba_batch_covariance.cpp).
+int joint_check(sba_batch* b, const double* rot, const double* tran);
+void joint_options(const sba_lm_options* opt, sba_lm_options* o);
 
 // sba_batch_select.cpp -- what the entry points that look at single matches share (sba_quantile.cpp).
 size_t batch_rows(const sba_batch* b);

@@ -78,6 +78,15 @@ bool finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]
 
 }  // namespace
 
+namespace sba {
+namespace batch {
+
+int joint_check(sba_batch* b, const double* rot, const double* tran) { return batch_joint_check(b, rot, tran); }
+void joint_options(const sba_lm_options* opt, sba_lm_options* o) { batch_joint_options(opt, o); }
+
+}  // namespace batch
+}  // namespace sba
+
 extern "C" {
 
 int sba_batch_eval_joint(sba_batch* b, const double* rot, const double* tran, double radius, const sba_lm_options* opt,

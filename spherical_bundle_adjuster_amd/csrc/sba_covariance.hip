@@ -8,6 +8,8 @@
 //   cov_depth_kernel   given Sigma_c (kernel argument): the same block from the same inputs, T = U^-1 W,
 //                      Sigma_dd,i = s (U^-1 + T Sigma_c T^T) s, three doubles per match
 // Bytes per match (f64 planes): reduce reads 64; depth reads 64 and writes 24.
+// The two per-match loops are sba_cov_reduce_loop.inc / sba_cov_depth_loop.inc, the one text this file and the batched form
+// (sba_batch_covariance.hip) both expand in their kernels' bodies.
 #include "sba_covariance.hpp"
 #include "sba_device.hpp"
 #include "sba_joint_core.hpp"
@@ -16,17 +18,6 @@ namespace sba {
 namespace {
 
 struct CovSigma { double c[36]; };
-
-// A lane's two matches of one stride step (JointRegs without the scaling planes, which a first pass never reads).
-template <typename ST>
-struct CovRegs {
-  double X[2], Y[2], Z[2], U[2], V[2], W[2], A[2], B[2];
-  __device__ __forceinline__ void load(const Planes& pl, const double* d1, const double* d2, size_t pr) {
-    JPair<ST>::load(pl.x1[0], pr, X); JPair<ST>::load(pl.x1[1], pr, Y); JPair<ST>::load(pl.x1[2], pr, Z);
-    JPair<ST>::load(pl.x2[0], pr, U); JPair<ST>::load(pl.x2[1], pr, V); JPair<ST>::load(pl.x2[2], pr, W);
-    JPair<double>::load(d1, pr, A); JPair<double>::load(d2, pr, B);
-  }
-};
 
 template <typename ST>
 __global__ __launch_bounds__(256, 2) void cov_reduce_kernel(Planes pl, const double* __restrict__ d1, const double* __restrict__ d2,
@@ -37,53 +28,8 @@ __global__ __launch_bounds__(256, 2) void cov_reduce_kernel(Planes pl, const dou
   double acc[COV_OUT_COUNT];
 #pragma unroll
   for (int k = 0; k < COV_OUT_COUNT; ++k) acc[k] = 0.0;
-  CovRegs<ST> cur, nxt;
-  if (pr < npairs) cur.load(pl, d1, d2, pr);
-  while (pr < npairs) {
-    const size_t pn = pr + stride;
-    if (pn < npairs) nxt.load(pl, d1, d2, pn);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const bool valid = 2 * pr + h < n;
-      JointBlock b;
-      joint_block(P, cur.X[h], cur.Y[h], cur.Z[h], cur.U[h], cur.V[h], cur.W[h], cur.A[h], cur.B[h], 1.0, 1.0, valid, b);
-      double z1[6], z2[6], Ui[3];
-      const bool ok = cov_block(b.U11, b.U12, b.U22, b.inv_det, b.w1, b.w2, min_sin2, z1, z2, Ui);
-      if (valid && ok) {
-        const double w = b.w;
-        double wA[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) wA[r][j] = w * b.A[r][j];
-        double ff[21];      // w F^T F (upper, row by row) of this match
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-#pragma unroll
-          for (int c = a; c < 3; ++c) ff[k++] = wA[0][a] * b.A[0][c] + wA[1][a] * b.A[1][c] + wA[2][a] * b.A[2][c];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) ff[k++] = wA[c][a];
-        }
-        ff[15] = w; ff[16] = 0.0; ff[17] = 0.0; ff[18] = w; ff[19] = 0.0; ff[20] = w;
-        k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-          for (int c = a; c < 6; ++c) {
-            acc[COV_OUT_S + k] += ff[k] - (b.w1[a] * z1[c] + b.w2[a] * z2[c]);
-            ++k;
-          }
-        acc[COV_OUT_COST] = __builtin_fma(0.5, b.rho, acc[COV_OUT_COST]);
-        acc[COV_OUT_SW] += w;
-        acc[COV_OUT_NUSED] += 1.0;
-      } else if (valid) {
-        acc[COV_OUT_NDEG] += 1.0;
-      }
-    }
-    cur = nxt;
-    pr = pn;
-  }
+  const IdentityMap map;
+#include "sba_cov_reduce_loop.inc"
   joint_block_fold<COV_OUT_COUNT, -1>(acc, red, partials + static_cast<size_t>(blockIdx.x) * COV_ROW);
 }
 
@@ -93,29 +39,14 @@ __global__ __launch_bounds__(256, 2) void cov_depth_kernel(Planes pl, const doub
                                                           JointParams P, double min_sin2, CovSigma sigma, double* __restrict__ out) {
   const size_t n = P.cur.n, npairs = (n + 1) / 2, stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   size_t pr = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  CovRegs<ST> cur, nxt;
-  if (pr < npairs) cur.load(pl, d1, d2, pr);
-  while (pr < npairs) {
-    const size_t pn = pr + stride;
-    if (pn < npairs) nxt.load(pl, d1, d2, pn);
-    double o[2][3];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const bool valid = 2 * pr + h < n;
-      JointBlock b;
-      joint_block(P, cur.X[h], cur.Y[h], cur.Z[h], cur.U[h], cur.V[h], cur.W[h], cur.A[h], cur.B[h], 1.0, 1.0, valid, b);
-      double z1[6], z2[6], Ui[3];
-      const bool ok = cov_block(b.U11, b.U12, b.U22, b.inv_det, b.w1, b.w2, min_sin2, z1, z2, Ui);
-      o[h][0] = __builtin_huge_val(); o[h][1] = __builtin_huge_val(); o[h][2] = 0.0;
-      if (ok) cov_depth_block(b.s1, b.s2, Ui, z1, z2, sigma.c, o[h]);
-      if (!valid) { o[h][0] = 0.0; o[h][1] = 0.0; o[h][2] = 0.0; }
-    }
-    joint_store_pair(out, 3 * pr, o[0][0], o[0][1]);
-    joint_store_pair(out, 3 * pr + 1, o[0][2], o[1][0]);
-    joint_store_pair(out, 3 * pr + 2, o[1][1], o[1][2]);
-    cur = nxt;
-    pr = pn;
-  }
+  const IdentityMap map;
+  const double* sigma_c = sigma.c;
+  const auto store = [out](size_t p, const double (&o)[2][3]) {
+    joint_store_pair(out, 3 * p, o[0][0], o[0][1]);
+    joint_store_pair(out, 3 * p + 1, o[0][2], o[1][0]);
+    joint_store_pair(out, 3 * p + 2, o[1][1], o[1][2]);
+  };
+#include "sba_cov_depth_loop.inc"
 }
 
 // [nblocks][COV_ROW] -> out[COV_OUT_COUNT]: every slot folded in a fixed order (one wave per slot at a time: lane l takes

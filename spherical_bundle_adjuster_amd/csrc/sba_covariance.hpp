@@ -1,6 +1,6 @@
 // Covariance of the joint solve at a point (rot, tran, d) -- what ceres::Covariance gives a Ceres user -- as two pieces
 // with no HIP in them: the per-match 2x2 block arithmetic both kernels of sba_covariance.hip run (cov_block, cov_depth_block)
-// and the host finish between the two passes (cov_finish).  The same source is driven on the CPU by
+// and the finish between the two passes (cov_finish: on the host for one problem, on the device for a batch).  The same source is driven on the CPU by
 // tests/test_covariance_host_cpu.py with blocks from the dense restatement.
 //
 // Robustified problem (sqrt(rho')-scaled Jacobian, Ceres' apply_loss_function = true), undamped (radius = inf), depth
@@ -68,13 +68,26 @@ SBA_HD inline void cov_depth_block(double s1, double s2, const double Ui[3], con
   out[2] = s1 * (Ui[1] + q12) * s2;
 }
 
-// Host finish: S (upper triangle, row by row, 21 entries) -> Sigma_c (cov, row-major 6 x 6, symmetric to the bit) and the
-// dimension m of the gauge's tangent space.  Project with detail::Param, Jacobi-scale to unit diagonal, Cholesky, invert,
-// un-scale, lift.  Returns false -- nothing written -- when n_used < m, S is not finite, or a pivot of the unit-diagonal
-// system is not above m * DBL_EPSILON (a rank-deficient gauge or scene).
-inline bool cov_finish(const double* S21, int tran_param, const double tran[3], long long n_used, double* cov, int* dim) {
+// The arrays of cov_finish: on the host an object on the stack, on the device the block's LDS (the loops below index them
+// with run-time bounds, which registers cannot serve).
+struct CovFinishWork {
+  sba_normal_eq ne;
+  detail::Param par;
+  double Sf[detail::kDim * detail::kDim], gf[detail::kDim], sc[detail::kDim], A[detail::kDim * detail::kDim];
+  double L[detail::kDim * detail::kDim], Li[detail::kDim * detail::kDim], Cf[detail::kDim * detail::kDim], PC[detail::kDim * detail::kDim];
+};
+
+// The finish between the two passes: S (upper triangle, row by row, 21 entries) -> Sigma_c (cov, row-major 6 x 6, symmetric to
+// the bit) and the dimension m of the gauge's tangent space.  Project with detail::Param, Jacobi-scale to unit diagonal,
+// Cholesky, invert, un-scale, lift.  Returns false -- nothing written -- when n_used < m, S is not finite, or a pivot of the
+// unit-diagonal system is not above m * DBL_EPSILON (a rank-deficient gauge or scene).  Host and device (thread 0 of
+// batch_cov_kernel) run this one text, unfused on either: their results agree to the bit.  wk: need not be initialised.
+SBA_HD inline bool cov_finish(const double* S21, int tran_param, const double tran[3], long long n_used, double* cov, int* dim,
+                              CovFinishWork* wk) {
   using namespace detail;
-  sba_normal_eq ne{};
+  sba_normal_eq& ne = wk->ne;
+  for (int a = 0; a < 6; ++a) ne.g[a] = 0.0;
+  ne.cost = 0.0; ne.sum_w = 0.0; ne.n_outlier = 0.0;
   int k = 0;
   for (int a = 0; a < 6; ++a)
     for (int b = a; b < 6; ++b) {
@@ -83,11 +96,11 @@ inline bool cov_finish(const double* S21, int tran_param, const double tran[3], 
       ne.H[6 * b + a] = S21[k];
       ++k;
     }
-  Param par;
+  Param& par = wk->par;
   par.build(SBA_MODE_RT, tran_param, tran);
   const int m = par.m;
   if (n_used < m) return false;
-  double Sf[kDim * kDim], gf[kDim], sc[kDim], A[kDim * kDim];
+  double *Sf = wk->Sf, *gf = wk->gf, *sc = wk->sc, *A = wk->A;
   par.project(ne, Sf, gf);
   for (int i = 0; i < m; ++i) {
     const double d = Sf[i * kDim + i];
@@ -97,7 +110,8 @@ inline bool cov_finish(const double* S21, int tran_param, const double tran[3], 
   for (int i = 0; i < m; ++i)
     for (int j = 0; j < m; ++j) A[i * kDim + j] = i == j ? 1.0 : sc[i] * Sf[(i < j ? i : j) * kDim + (i < j ? j : i)] * sc[j];
   // A = L L^T
-  double L[kDim * kDim] = {0}, Li[kDim * kDim] = {0};
+  double *L = wk->L, *Li = wk->Li, *Cf = wk->Cf, *PC = wk->PC;
+  for (int i = 0; i < kDim * kDim; ++i) { L[i] = 0.0; Li[i] = 0.0; Cf[i] = 0.0; PC[i] = 0.0; }
   const double floor_pivot = m * DBL_EPSILON;
   for (int i = 0; i < m; ++i)
     for (int j = 0; j <= i; ++j) {
@@ -118,7 +132,6 @@ inline bool cov_finish(const double* S21, int tran_param, const double tran[3], 
       Li[i * kDim + c] = s / L[i * kDim + i];
     }
   // A^-1 = L^-T L^-1, un-scaled: upper triangle, mirrored
-  double Cf[kDim * kDim] = {0};
   for (int i = 0; i < m; ++i)
     for (int j = i; j < m; ++j) {
       double s = 0.0;
@@ -129,7 +142,6 @@ inline bool cov_finish(const double* S21, int tran_param, const double tran[3], 
       Cf[j * kDim + i] = s;
     }
   // lift: P Cf P^T
-  double PC[kDim * kDim] = {0};
   for (int a = 0; a < 6; ++a)
     for (int j = 0; j < m; ++j) {
       double s = 0.0;
@@ -145,6 +157,12 @@ inline bool cov_finish(const double* S21, int tran_param, const double tran[3], 
     }
   *dim = m;
   return true;
+}
+
+// ... with its arrays on the caller's stack: the host's form.
+SBA_HD inline bool cov_finish(const double* S21, int tran_param, const double tran[3], long long n_used, double* cov, int* dim) {
+  CovFinishWork wk;
+  return cov_finish(S21, tran_param, tran, n_used, cov, dim, &wk);
 }
 
 }  // namespace sba

@@ -455,6 +455,27 @@ inline int batch_joint_pass_bound(const sba_lm_options& opt) {
   return static_cast<int>(2 * its + 2);
 }
 
+// Batched joint covariance (sba_batch_covariance.hip): ONE 256-thread block per pair runs the pair's whole covariance -- reduce
+// (the body of cov_reduce_kernel), finish (cov_finish by thread 0, its arrays and Sigma_c in LDS), depth (the body of
+// cov_depth_kernel, rows to out[offsets[pair] + i][3]) -- or, under the lock-step driver, the phases `phases` names.
+// BatchCovRec: the pair's record in mapped pinned host memory.  In: rot, tran; refused != 0 marks a pair that must fail (a
+// non-finite point); without kCovFinish also sigma and dim_status (the host's finish).  Out: with kCovReduce the COV_OUT_* slots
+// in row, with kCovFinish sigma (NaN for a failed pair) and dim_status = dim | failed << 32.
+enum { kCovReduce = 1, kCovFinish = 2, kCovDepth = 4 };
+struct BatchCovRec {
+  double rot[3], tran[3];
+  double row[32];               // COV_ROW (sba_covariance.hpp) doubles, COV_OUT_COUNT used
+  double sigma[36];
+  unsigned long long dim_status;
+  unsigned long long refused;
+};
+static_assert(sizeof(BatchCovRec) == 608, "BatchCovRec layout");
+// ticket: one zeroed device word; seq_host_dev receives `seq` once every pair's block has delivered.  out (may be null: no
+// depth phase): [total][3] doubles in caller row order, offsets_dev relative to the first row.
+hipError_t launch_batch_cov(int store, const Planes& pl, const PairDesc* desc, int num_pairs, const sba_lm_options& opt,
+                            double min_sin2, int phases, const unsigned long long* offsets_dev, double* out, BatchCovRec* rec,
+                            unsigned int* ticket, unsigned long long* seq_host_dev, unsigned long long seq, hipStream_t stream);
+
 // 8-point initial guess, device part (.cpp:53-68): A^T A of the kron(left, right) rows for 64 interleaved groups.
 // groups_dev: [64][45]; partials: [grid][45][64] scratch.
 hipError_t launch_epipolar_moments(int store, const Planes& pl, size_t n, double* partials, int grid,

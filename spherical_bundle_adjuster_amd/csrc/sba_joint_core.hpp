@@ -53,6 +53,18 @@ struct JointRegs {
   }
 };
 
+// The same without the scaling planes, which a first pass never reads: what the covariance's two loops load
+// (sba_cov_reduce_loop.inc / sba_cov_depth_loop.inc).
+template <typename ST>
+struct CovRegs {
+  double X[2], Y[2], Z[2], U[2], V[2], W[2], A[2], B[2];
+  __device__ __forceinline__ void load(const Planes& pl, const double* d1, const double* d2, size_t pr) {
+    JPair<ST>::load(pl.x1[0], pr, X); JPair<ST>::load(pl.x1[1], pr, Y); JPair<ST>::load(pl.x1[2], pr, Z);
+    JPair<ST>::load(pl.x2[0], pr, U); JPair<ST>::load(pl.x2[1], pr, V); JPair<ST>::load(pl.x2[2], pr, W);
+    JPair<double>::load(d1, pr, A); JPair<double>::load(d2, pr, B);
+  }
+};
+
 // The per-match block at the current point: residual, Huber weight, Jacobian pieces, the scaled damped 2x2 depth block.
 // Both passes call this very function with the same inputs, so U, W and g_d agree to the bit between the passes.
 struct JointBlock {

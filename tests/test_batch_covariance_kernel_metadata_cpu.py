@@ -1,0 +1,61 @@
+"""CPU: the code-object METADATA of the batched covariance kernel (csrc/sba_batch_covariance.hip compiled for gfx950 with the
+Makefile's flags; hipcc cross-compiles): batch_cov_kernel exists for f64 and f32 planes, uses no scratch memory -- thread 0's
+cov_finish keeps its arrays in LDS, a spill would sit in the hot loops -- and its registers and LDS allow the two 256-thread
+blocks per CU its launch bounds ask for.  Only the .amdgpu_metadata records are read."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "spherical_bundle_adjuster_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+pytestmark = pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not available")
+
+REGISTER_FILE = 512      # unified vector registers per lane of a gfx950 SIMD (vector + accumulation registers)
+GRANULE = 8              # allocation granularity
+
+
+@pytest.fixture(scope="module")
+def metadata(tmp_path_factory):
+    """kernel name -> {field: int} from the .amdgpu_metadata records."""
+    flags = subprocess.run(["make", "-s", "-C", CSRC, "print-flags"], check=True, capture_output=True, text=True).stdout.split()
+    out = tmp_path_factory.mktemp("batch_cov_meta") / "sba_batch_covariance.s"
+    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
+    subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(CSRC, "sba_batch_covariance.hip"), "-o", str(out)],
+                   check=True, capture_output=True, cwd=CSRC)
+    text = out.read_text()
+    meta = text[text.index(".amdgpu_metadata"):text.index(".end_amdgpu_metadata")]
+    kernels = {}
+    for rec in meta.split("  - .agpr_count:")[1:]:
+        rec = ".agpr_count:" + rec
+        fields = dict(re.findall(r"\.(\w+):\s+(\S+)", rec))
+        kernels[fields["name"]] = {k: int(v) for k, v in fields.items() if re.fullmatch(r"\d+", v)}
+    return kernels
+
+
+def test_both_instances_are_compiled(metadata):
+    inst = sorted(k for k in metadata if "batch_cov_kernel" in k)
+    assert len(inst) == 2 and any("IdE" in k for k in inst) and any("IfE" in k for k in inst), list(metadata)
+    assert len(metadata) == 2, list(metadata)
+
+
+def test_no_scratch_and_a_256_thread_block(metadata):
+    for k, f in metadata.items():
+        assert f["private_segment_fixed_size"] == 0, (k, f)
+        assert f["vgpr_spill_count"] == 0, (k, f)
+        assert f["max_flat_workgroup_size"] == 256, (k, f)
+
+
+def test_two_blocks_per_cu(metadata):
+    """A 256-thread block is one wave per SIMD; two resident blocks need two waves' registers in the 512-entry file and twice
+    the block's LDS in the 64 KiB a workgroup may address."""
+    for k, f in metadata.items():
+        regs = -(-(f["vgpr_count"] + f["agpr_count"]) // GRANULE) * GRANULE
+        print(f"{k}: {f['vgpr_count']} vector + {f['agpr_count']} accumulation registers, {f['sgpr_count']} scalar "
+              f"({f['sgpr_spill_count']} spilled), {f['group_segment_fixed_size']} B LDS")
+        assert REGISTER_FILE // regs >= 2, (k, f)
+        assert 2 * f["group_segment_fixed_size"] <= 64 * 1024, (k, f)
