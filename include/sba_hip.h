@@ -385,6 +385,41 @@ int sba_problem_covariance_joint(sba_problem* p, const double rot[3], const doub
                                  const sba_lm_options* opt, double min_sin2_parallax,
                                  sba_joint_cov* out, double* depth_cov /* double[3n] or NULL */);
 
+/* ---- triangulated structure: one 3-D point per match, its 3 x 3 covariance, and a cut driven by it ---- */
+/* At (rot, tran) and the handle's depths, in camera 2's frame (the frame of the residual), with u_i = R(rot) x1_i:
+ *     X_i = ((d1_i u_i - tran) + d2_i x2_i) / 2                   the midpoint of the two ray ends
+ *     Sigma_X,i = G_d s_i U_i^-1 s_i G_d^T + K_i cov K_i^T        G_d = [u_i | x2_i] / 2,  K_i = -[A_i | I] / 2 - G_d s_i U_i^-1 W_i
+ *     q_i = trace(Sigma_X,i) / (X_i . X_i)                        dimensionless: independent of the gauge's scale
+ * -- the covariance of X_i under the joint covariance of sba_problem_covariance_joint over (d_i, rot, tran), the depth-camera
+ * cross blocks -s_i U_i^-1 W_i cov included.  Unscaled like that covariance: multiply Sigma_X and q by sigma^2 = 2 cost / dof.
+ * xyz [3n], xyz_cov [6n] (per match xx, yy, zz, xy, xz, yz) and score [n] (q) may each be NULL; an output that is not asked
+ * for is not computed.  A degenerate match (the rule and min_sin2_parallax of sba_problem_covariance_joint) keeps its X_i as
+ * computed, has the covariance row (+inf, +inf, +inf, 0, 0, 0) and q_i = +inf, and adds nothing to the camera system.
+ * out, opt, the refusals and SBA_ERR_NUMERIC are those of sba_problem_covariance_joint (same bits in out); on failure nothing
+ * is written.  Three launches: that call's reduce pass, its host finish, one streaming pass.  No value depends on a
+ * reduction beyond cov: the same bits on every run and for every grid.  The handle's depths and planes are not touched.  */
+int sba_problem_structure_joint(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
+                                double min_sin2_parallax, sba_joint_cov* out, double* xyz /* double[3n] or NULL */,
+                                double* xyz_cov /* double[6n] or NULL */, double* score /* double[n] or NULL */);
+/* The same with the three destinations in DEVICE memory (for example torch tensors): the kernel stores straight into them
+ * and nothing but `out` crosses to the host.  Each pointer must be 16-byte aligned (SBA_ERR_INVALID_ARG otherwise).  The work
+ * is enqueued on the handle's stream and the call returns after that stream has been waited for.                       */
+int sba_problem_structure_joint_device(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
+                                       double min_sin2_parallax, sba_joint_cov* out, double* xyz, double* xyz_cov,
+                                       double* score);
+/* values[j] = the ranks[j]-th smallest (0-based) of the scores q_i above, selected on the device as
+ * sba_problem_residual_order_stats selects: bit for bit an element of `score`, +inf (degenerate matches) above every finite
+ * score, NaN above +inf.  1 <= num_ranks <= 8, every ranks[j] < n.                                                      */
+int sba_problem_structure_order_stats(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
+                                      double min_sin2_parallax, const size_t* ranks, int num_ranks, double* values);
+/* *threshold = scale * q_(rank) (one IEEE f64 multiplication; scale finite and >= 0), then the matches with
+ * q_i <= *threshold stay, through the compaction of sba_problem_compact as in sba_problem_keep_below: afterwards the handle is
+ * what a fresh upload of the kept matches would be.  A NaN score is dropped; a degenerate match stays only under a threshold
+ * of +inf.  The cut is homogeneous in sigma^2, so the unscaled scores serve.                                             */
+int sba_problem_structure_keep_below(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
+                                     double min_sin2_parallax, size_t rank, double scale, double* threshold, size_t* n_kept,
+                                     long long* kept_index);
+
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other
  * ranks by any host channel, then every rank calls sba_problem_comm_init_rank.  After that

@@ -132,6 +132,14 @@ SIGNATURES = {
     "sba_problem_eval_joint": (C.c_int, [_vp, _dp, _dp, C.c_double, C.POINTER(LmOptions), C.POINTER(JointEq)]),
     "sba_problem_solve_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(LmSummary), _vp]),
     "sba_problem_covariance_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(JointCov), _dp]),
+    "sba_problem_structure_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(JointCov), _dp, _dp,
+                                              _dp]),
+    "sba_problem_structure_joint_device": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(JointCov), _vp,
+                                                     _vp, _vp]),
+    "sba_problem_structure_order_stats": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(C.c_size_t),
+                                                    C.c_int, _dp]),
+    "sba_problem_structure_keep_below": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.c_size_t, C.c_double,
+                                                   _dp, C.POINTER(C.c_size_t), _vp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

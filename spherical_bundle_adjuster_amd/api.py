@@ -59,6 +59,24 @@ class JointCovariance:
 
 
 @dataclass
+class JointStructure:
+    """Triangulated landmarks at a point (Problem.structure_joint), in camera 2's frame: per match the midpoint of the two
+    ray ends, its 3 x 3 covariance under the joint covariance (depth-camera cross blocks included) and the dimensionless score
+    trace(cov) / |xyz|^2.  Unscaled like JointCovariance: multiply cov and score by sigma2.  A degenerate match keeps its xyz,
+    has the cov row (inf, inf, inf, 0, 0, 0) and score inf."""
+    xyz: np.ndarray                # (n, 3)
+    cov: np.ndarray | None         # (n, 6): xx, yy, zz, xy, xz, yz
+    score: np.ndarray | None       # (n,)
+    pose: JointCovariance          # what covariance_joint(depths=False) returns at the same arguments, bit for bit
+
+    def __getattr__(self, name):
+        """cost, sum_w, n_used, n_degenerate, dim, dof and sigma2 read through to `pose`."""
+        if name in ("cost", "sum_w", "n_used", "n_degenerate", "dim", "dof", "sigma2"):
+            return getattr(self.pose, name)
+        raise AttributeError(name)
+
+
+@dataclass
 class BatchJointCovariance:
     """Covariance of every pair's joint problem (Batch.covariance_joint).  A pair with status != 0 has no covariance: its cov
     and its depth_cov rows are NaN.  Multiply a pair's blocks by its sigma2 for residuals of unknown variance."""
@@ -542,6 +560,71 @@ class Problem:
                                                                      None if dd is None else _dptr(dd)))
         return JointCovariance(np.array(res.cov, dtype=np.float64).reshape(6, 6), dd, float(res.cost), float(res.sum_w),
                                int(res.n_used), int(res.n_degenerate), int(res.dim), int(res.dof))
+
+    @staticmethod
+    def _joint_cov(res) -> JointCovariance:
+        return JointCovariance(np.array(res.cov, dtype=np.float64).reshape(6, 6), None, float(res.cost), float(res.sum_w),
+                               int(res.n_used), int(res.n_degenerate), int(res.dim), int(res.dof))
+
+    def structure_joint(self, rot, tran, options: cabi.LmOptions | None = None, min_sin2_parallax: float = 0.0,
+                        cov: bool = True, score: bool = True, xyz: bool = True) -> JointStructure:
+        """One 3-D point per match at (rot, tran) and the handle's depths, with its covariance and score (JointStructure).
+        cov / score / xyz = False skips that output (it is then None).  Degeneracy rule, options and errors as
+        covariance_joint.  The handle's state is not touched."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        n = self.size
+        res = cabi.JointCov()
+        X = np.zeros((n, 3)) if xyz else None
+        Cv = np.zeros((n, 6)) if cov else None
+        q = np.zeros(n) if score else None
+        ptr = lambda a: None if a is None else _dptr(a)
+        cabi.check(self._lib, self._lib.sba_problem_structure_joint(self._h, _dptr(rot), _dptr(tran),
+                                                                    None if options is None else C.byref(options),
+                                                                    float(min_sin2_parallax), C.byref(res), ptr(X), ptr(Cv), ptr(q)))
+        return JointStructure(X, Cv, q, self._joint_cov(res))
+
+    def structure_joint_into(self, xyz_ptr, cov_ptr, score_ptr, rot, tran, options: cabi.LmOptions | None = None,
+                             min_sin2_parallax: float = 0.0) -> JointCovariance:
+        """structure_joint with the outputs stored straight into DEVICE memory: xyz_ptr / cov_ptr / score_ptr are device
+        addresses (for example ``tensor.data_ptr()`` of float64 tensors of n * 3, n * 6 and n elements on the handle's
+        device), 16-byte aligned, 0 or None to skip an output.  Returns the pose record; nothing else crosses to the host."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        res = cabi.JointCov()
+        vp = lambda a: C.c_void_p(int(a)) if a else None
+        cabi.check(self._lib, self._lib.sba_problem_structure_joint_device(self._h, _dptr(rot), _dptr(tran),
+                                                                           None if options is None else C.byref(options),
+                                                                           float(min_sin2_parallax), C.byref(res), vp(xyz_ptr),
+                                                                           vp(cov_ptr), vp(score_ptr)))
+        return self._joint_cov(res)
+
+    def structure_order_stats(self, rot, tran, ranks, options: cabi.LmOptions | None = None,
+                              min_sin2_parallax: float = 0.0) -> np.ndarray:
+        """The ranks[j]-th smallest (0-based) of structure_joint's scores, selected on the device: bit for bit elements of
+        that array; inf (degenerate matches) sorts above every finite score, NaN above inf.  Up to 8 ranks."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        r = _ranks(ranks).reshape(-1)
+        vals = np.empty(r.shape[0])
+        cabi.check(self._lib, self._lib.sba_problem_structure_order_stats(
+            self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options), float(min_sin2_parallax),
+            r.ctypes.data_as(C.POINTER(C.c_size_t)), r.shape[0], _dptr(vals)))
+        return vals
+
+    def structure_keep_below(self, rot, tran, prob, scale, options: cabi.LmOptions | None = None,
+                             min_sin2_parallax: float = 0.0):
+        """Keep the matches with score <= scale * (the `prob` quantile of the scores, rank `quantile_rank`), selected,
+        flagged and compacted on the device as keep_below does; the handle then equals a fresh upload of the kept matches.
+        Degenerate matches (score inf) go unless the threshold itself is inf; a NaN score is dropped.  Returns (original
+        indices of the kept matches (np.int64), the threshold).  `scale` has no default: how much worse than the typical
+        landmark a landmark may be is the caller's choice."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        n = self.size
+        rank = int(quantile_rank(prob, n).reshape(-1)[0]) if n > 0 else 0      # an empty handle: the library's refusal answers
+        idx = np.empty(max(n, 1), dtype=np.int64)
+        kept, thr = C.c_size_t(0), C.c_double(0.0)
+        cabi.check(self._lib, self._lib.sba_problem_structure_keep_below(
+            self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options), float(min_sin2_parallax), rank,
+            float(scale), C.byref(thr), C.byref(kept), idx.ctypes.data_as(C.c_void_p)))
+        return idx[:kept.value].copy(), thr.value
 
     # -- 8-point initial guess ----------------------------------------------------------------------
     def epipolar_moments(self) -> np.ndarray:

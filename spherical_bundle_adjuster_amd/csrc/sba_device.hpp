@@ -418,6 +418,20 @@ hipError_t launch_cov_reduce(int store, const Planes& pl, const double* d1, cons
 hipError_t launch_cov_depth(int store, const Planes& pl, const double* d1, const double* d2, const JointParams& prm,
                             double min_sin2, const double sigma_c[36], double* out, int grid, hipStream_t stream);
 
+// Triangulated landmarks with their covariances (sba_structure.hip; algebra: sba_structure.hpp).  params_dev: device memory,
+// staged in LDS by the kernel -- prm as for launch_cov_reduce, sigma_c the ambient 6 x 6 camera covariance.  xyz [n][3],
+// cov [n][6] (xx, yy, zz, xy, xz, yz), score [n]: device pointers, 16-byte aligned, any of them null (that output is compiled
+// out); exactly n rows are written.
+struct StructureParams {
+  JointParams prm;
+  double sigma_c[36];
+  double min_sin2;
+  double pad_;
+};
+hipError_t structure_blocks_per_cu(int store, int* blocks);   // resident 256-thread blocks per CU of the all-outputs kernel
+hipError_t launch_structure(int store, const Planes& pl, const double* d1, const double* d2, const StructureParams* params_dev,
+                            double* xyz, double* cov, double* score, int grid, hipStream_t stream);
+
 // Batched joint solve (sba_batch_joint.hip): ONE 256-thread block per pair -- the reduce body's ~350 registers fit one wave per
 // SIMD only, a 512-thread block would halve the budget and spill into the hot loop.  BatchJointPass: what the lock-step driver
 // hands over per pair and pass (mapped pinned host memory): the pass kind (kJointReduce / kJointStep), the current camera, for a

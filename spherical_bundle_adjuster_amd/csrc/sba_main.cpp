@@ -1,9 +1,11 @@
 // Command-line driver with the reference's argument contract (main/main.cpp:8-27):
-//   sba_main [--joint [--covariance]] [--reject Q,SCALE] <L> <R> <exp roll> <exp pitch> <exp yaw> <exp Tx> <exp Ty> <exp Tz> <exp d>
+//   sba_main [--joint [--covariance] [--structure FILE]] [--reject Q,SCALE] <L> <R> <exp roll> <exp pitch> <exp yaw> <exp Tx> <exp Ty> <exp Tz> <exp d>
 // --joint (anywhere on the line; not in the reference): refine depths, rotation and translation together after the
 // tran-only stage (spherical_bundle_adjuster::set_joint_refinement).  Without it the run is the reference's three stages.
 // --covariance (only together with --joint; not in the reference): after the joint stage print one more line, the 1-sigma of
 // the rotation vector (degrees) and of the translation from the joint problem's covariance (set_joint_covariance).
+// --structure FILE (only together with --joint; not in the reference): after the joint stage write the triangulated landmarks as
+// an ASCII PLY, one vertex "x y z q" per match: the point in camera 2's frame and its uncertainty score (set_structure_output).
 // --reject Q,SCALE (not in the reference): after the last stage drop the matches whose squared residual norm exceeds SCALE
 // times its Q quantile, run the stages once more on the rest and report the cut (set_outlier_rejection).
 // With OpenCV (SBA_WITH_OPENCV) <L>/<R> are ERP images and a matcher must be linked in by the
@@ -41,19 +43,22 @@ bool read_keypoints(const char* path, std::vector<cv::KeyPoint>* out, std::vecto
 int main(int argc, char** argv) {
   bool joint = false, covariance = false, reject = false;
   double reject_q = 0.0, reject_scale = 0.0;
+  const char* structure = nullptr;
   {
     int kept = 1;
     for (int i = 1; i < argc; ++i) {
       if (std::strcmp(argv[i], "--joint") == 0) joint = true;
       else if (std::strcmp(argv[i], "--covariance") == 0) covariance = true;
+      else if (std::strcmp(argv[i], "--structure") == 0 && i + 1 < argc) structure = argv[++i];
       else if (std::strcmp(argv[i], "--reject") == 0 && i + 1 < argc &&
                std::sscanf(argv[i + 1], "%lf,%lf", &reject_q, &reject_scale) == 2) { reject = true; ++i; }
       else argv[kept++] = argv[i];
     }
     argc = kept;
   }
-  if (argc != 10 || (covariance && !joint)) {
+  if (argc != 10 || (covariance && !joint) || (structure && !joint)) {
     if (covariance && !joint) std::cout << "--covariance needs --joint" << std::endl;
+    if (structure && !joint) std::cout << "--structure needs --joint" << std::endl;
     std::cout << "usage : spherical_bundle_adjuster.out <L image> <R image> <exp roll> <exp pitch> <exp yaw> "
                  "<exp Tx> <exp Ty> <exp Tz> <exp d>" << std::endl;
     return 0;   // the reference returns 0 on a usage error too (main/main.cpp:11)
@@ -65,6 +70,7 @@ int main(int argc, char** argv) {
   if (const char* env = std::getenv("SBA_INITIAL_GUESS")) sph_ba.set_initial_guess(env[0] != '0');
   sph_ba.set_joint_refinement(joint);
   sph_ba.set_joint_covariance(covariance);
+  if (structure) sph_ba.set_structure_output(structure);
   if (reject) sph_ba.set_outlier_rejection(reject_q, reject_scale);
   std::vector<cv::KeyPoint> left_key, right_key;
   std::vector<float> left_desc, right_desc;

@@ -5,6 +5,7 @@
 //   sba_select.cpp     per-match residuals and compaction of the matches
 //   sba_joint.cpp      joint solve (depths, rotation and translation together) entry points
 //   sba_covariance.cpp covariance of the joint solve at a point (pose 6x6, per-match depth blocks)
+//   sba_structure.cpp  triangulated landmarks with their covariances at a point, and the cut driven by their score
 //   sba_quantile.cpp   order statistics of the per-match squared residual norms and the keep-rule built on them
 // Internal: nothing here is exported from the library.
 #pragma once
@@ -16,6 +17,7 @@
 #include "../../include/sba_hip.h"
 #include "sba_device.hpp"
 #include "sba_internal.hpp"
+#include "sba_quantile.hpp"
 #include "sba_resident.hpp"
 
 // ---- the handle ---------------------------------------------------------------------------------
@@ -42,6 +44,7 @@ struct sba_problem {
   unsigned long long joint_seq = 0;
   int joint_occ[2] = {0, 0};       // resident blocks per CU of joint_reduce_kernel per [store]
   int cov_occ[2] = {0, 0};         // ... and of cov_reduce_kernel (sba_covariance.cpp; its rows and outputs share depth_scratch)
+  int structure_occ[2] = {0, 0};   // ... and of structure_kernel (sba_structure.cpp; parameters and host-form outputs share depth_scratch)
   void* subset_scratch = nullptr;  // reference sampling: [trials][45] moments, then the [trials][m] index lists; kept across calls
   size_t subset_scratch_bytes = 0;
   void* select_scratch = nullptr;  // per-match residuals: inlier count, then the requested outputs; kept across calls
@@ -218,6 +221,32 @@ struct CompactWork {
 };
 int compact_alloc(sba_problem* p, CompactWork* w);
 int compact_rows(sba_problem* p, CompactWork& w, size_t* n_kept, long long* kept_index);
+
+// sba_covariance.cpp -- everything sba_problem_covariance_joint does before its per-match pass, for the entry points that
+// follow it with a per-match pass of their own (sba_structure.cpp): argument checks and refusals, the reduce pass, the host
+// finish.  front_elems: doubles the caller wants at the front of the handle's d-only scratch (cp->front, 256-byte aligned).
+// On success cp holds the planes, the pass's JointParams, the grid and the result record; on failure nothing is enqueued
+// beyond the reduce pass and the handle stays usable.
+struct CovPass {
+  sba::Planes pl;
+  sba::JointParams prm;
+  int grid = 0;
+  sba_joint_cov res;
+  double* front = nullptr;
+};
+int cov_first_pass(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt, double min_sin2_parallax,
+                   size_t front_elems, CovPass* cp);
+
+// sba_quantile.cpp -- the selection over a plane of n per-match values that is already on the device, for callers that
+// write the plane themselves (sba_structure.cpp).  select_plane: the handle's select scratch sized for num_ranks ranks,
+// *plane = its per-match plane (plane_elems doubles).  select_enqueue: ranks (and, with scale, the threshold scale *
+// value[0]) over plane[0 .. n); host_offsets (2 words), ranks and scale stay valid until the caller has waited for the stream.
+// select_values / select_keep: what sba_problem_residual_order_stats / sba_problem_keep_below do after their selection.
+int select_plane(sba_problem* p, int num_ranks, sba::SelectScratch* s, double** plane);
+int select_enqueue(sba_problem* p, const sba::SelectScratch& s, const size_t* ranks, int num_ranks, const double* scale,
+                   unsigned long long* host_offsets);
+int select_values(sba_problem* p, const sba::SelectScratch& s, int num_ranks, double* values);
+int select_keep(sba_problem* p, const sba::SelectScratch& s, double* threshold, size_t* n_kept, long long* kept_index);
 
 // sba_transport.cpp
 int allreduce_pack(sba_problem* p);                                  // p->pack_dev (24 doubles), then hand-over to the host

@@ -11,26 +11,11 @@
 
 static_assert(sizeof(size_t) == sizeof(unsigned long long), "ranks travel as 64-bit words");
 
+using sba::SelectScratch;
+
 namespace {
 
 size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
-
-// The device scratch of one selection, carved from the handle's select_scratch: per-pair inlier counts (the residual kernel's
-// by-product) | kept counts | a single problem's two row offsets | ranks | values | scales | thresholds | selection states |
-// histograms | the s plane.
-struct SelectScratch {
-  unsigned long long* n_inlier = nullptr;
-  unsigned long long* kept = nullptr;
-  unsigned long long* offsets = nullptr;
-  unsigned long long* ranks = nullptr;
-  double* values = nullptr;
-  double* scale = nullptr;
-  double* thr = nullptr;
-  sba::SelectState* state = nullptr;
-  unsigned long long* hist = nullptr;
-  double* sq = nullptr;
-  size_t bytes = 0;
-};
 
 SelectScratch carve(char* base, size_t pairs, size_t num_ranks, size_t sq_elems) {
   SelectScratch s;
@@ -107,11 +92,10 @@ int enqueue_problem_select(sba_problem* p, int depth_mode, const double rot[3], 
   sba::SweepParams prm;
   sba::make_sweep_params(n, depth_mode, rot, tran, d1, d2, 0.0, &prm);
 
-  const size_t need = carve(nullptr, 1, num_ranks, p->plane_elems).bytes;
-  rc = ensure_scratch(&p->select_scratch, &p->select_scratch_bytes, need, p->stream, &p->poisoned);
+  double* plane = nullptr;
+  rc = sba::shim::select_plane(p, num_ranks, out, &plane);
   if (rc) return rc;
-  const SelectScratch s = carve(static_cast<char*>(p->select_scratch), 1, num_ranks, p->plane_elems);
-  *out = s;
+  const SelectScratch& s = *out;
 
   sba::ResidualOut res;
   res.e = nullptr;
@@ -124,9 +108,28 @@ int enqueue_problem_select(sba_problem* p, int depth_mode, const double rot[3], 
   const int per_cu = p->blocks_per_cu_cap > 0 ? p->blocks_per_cu_cap : 2;
   const int grid = static_cast<int>(std::min<size_t>(want, static_cast<size_t>(p->num_cus) * per_cu));
   SBA_TRY_HIP(sba::launch_residuals(kernel_depth, p->store, 2, pl, prm, res, grid, p->stream));
+  return sba::shim::select_enqueue(p, s, ranks, num_ranks, scale, host_offsets);
+}
 
+}  // namespace
+
+// ---- the selection over a plane that is already on the device (sba_problem.hpp) --------------------------------------------
+namespace sba {
+namespace shim {
+
+int select_plane(sba_problem* p, int num_ranks, SelectScratch* s, double** plane) {
+  const size_t need = carve(nullptr, 1, num_ranks, p->plane_elems).bytes;
+  const int rc = ensure_scratch(&p->select_scratch, &p->select_scratch_bytes, need, p->stream, &p->poisoned);
+  if (rc) return rc;
+  *s = carve(static_cast<char*>(p->select_scratch), 1, num_ranks, p->plane_elems);
+  *plane = s->sq;
+  return SBA_OK;
+}
+
+int select_enqueue(sba_problem* p, const SelectScratch& s, const size_t* ranks, int num_ranks, const double* scale,
+                   unsigned long long* host_offsets) {
   host_offsets[0] = 0;
-  host_offsets[1] = n;
+  host_offsets[1] = p->n;
   SBA_TRY_HIP(hipMemcpyAsync(s.offsets, host_offsets, 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, p->stream));
   SBA_TRY_HIP(hipMemcpyAsync(s.ranks, ranks, num_ranks * sizeof(unsigned long long), hipMemcpyHostToDevice, p->stream));
   if (scale) SBA_TRY_HIP(hipMemcpyAsync(s.scale, scale, sizeof(double), hipMemcpyHostToDevice, p->stream));
@@ -134,6 +137,34 @@ int enqueue_problem_select(sba_problem* p, int depth_mode, const double rot[3], 
                                       s.hist, s.values, s.thr, p->stream));
   return SBA_OK;
 }
+
+int select_values(sba_problem* p, const SelectScratch& s, int num_ranks, double* values) {
+  SBA_TRY_HIP(hipMemcpyAsync(values, s.values, num_ranks * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  return sba::stream_wait(p->stream, "order statistics", &p->poisoned);
+}
+
+int select_keep(sba_problem* p, const SelectScratch& s, double* threshold, size_t* n_kept, long long* kept_index) {
+  // The threshold kernel writes the compaction's keep bytes: the mask never leaves the device.
+  CompactWork w(&p->poisoned);
+  int rc = compact_alloc(p, &w);
+  if (rc) return rc;
+  SBA_TRY_HIP(sba::launch_keep_below(s.sq, s.offsets, 1, select_grid(p), s.thr, w.keep, s.kept, p->stream));
+  double thr = 0.0;
+  unsigned long long kept = 0;
+  SBA_TRY_HIP(hipMemcpyAsync(&thr, s.thr, sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  SBA_TRY_HIP(hipMemcpyAsync(&kept, s.kept, sizeof(kept), hipMemcpyDeviceToHost, p->stream));
+  rc = compact_rows(p, w, n_kept, kept_index);   // waits for the stream before it sizes the new planes
+  if (rc) return rc;
+  *threshold = thr;
+  if (kept != *n_kept)
+    return sba::set_error(SBA_ERR_NUMERIC, "the threshold kernel kept %llu matches, the compaction %zu", kept, *n_kept);
+  return SBA_OK;
+}
+
+}  // namespace shim
+}  // namespace sba
+
+namespace {
 
 // ---- batch ---------------------------------------------------------------------------------------------------------------
 int check_batch(const sba_batch* b, int depth_mode, const double* rot, const double* tran, const size_t* ranks, int num_ranks) {
@@ -184,8 +215,7 @@ int sba_problem_residual_order_stats(sba_problem* p, int depth_mode, const doubl
   SelectScratch s;
   rc = enqueue_problem_select(p, depth_mode, rot, tran, d1, d2, ranks, num_ranks, nullptr, host_offsets, &s);
   if (rc) return rc;
-  SBA_TRY_HIP(hipMemcpyAsync(values, s.values, num_ranks * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-  return sba::stream_wait(p->stream, "order statistics", &p->poisoned);
+  return sba::shim::select_values(p, s, num_ranks, values);
 }
 
 int sba_problem_keep_below(sba_problem* p, int depth_mode, const double rot[3], const double tran[3], double d1, double d2,
@@ -199,21 +229,7 @@ int sba_problem_keep_below(sba_problem* p, int depth_mode, const double rot[3], 
   SelectScratch s;
   rc = enqueue_problem_select(p, depth_mode, rot, tran, d1, d2, &rank, 1, &scale, host_offsets, &s);
   if (rc) return rc;
-  // The threshold kernel writes the compaction's keep bytes: the mask never leaves the device.
-  sba::shim::CompactWork w(&p->poisoned);
-  rc = sba::shim::compact_alloc(p, &w);
-  if (rc) return rc;
-  SBA_TRY_HIP(sba::launch_keep_below(s.sq, s.offsets, 1, select_grid(p), s.thr, w.keep, s.kept, p->stream));
-  double thr = 0.0;
-  unsigned long long kept = 0;
-  SBA_TRY_HIP(hipMemcpyAsync(&thr, s.thr, sizeof(double), hipMemcpyDeviceToHost, p->stream));
-  SBA_TRY_HIP(hipMemcpyAsync(&kept, s.kept, sizeof(kept), hipMemcpyDeviceToHost, p->stream));
-  rc = sba::shim::compact_rows(p, w, n_kept, kept_index);   // waits for the stream before it sizes the new planes
-  if (rc) return rc;
-  *threshold = thr;
-  if (kept != *n_kept)
-    return sba::set_error(SBA_ERR_NUMERIC, "the threshold kernel kept %llu matches, the compaction %zu", kept, *n_kept);
-  return SBA_OK;
+  return sba::shim::select_keep(p, s, threshold, n_kept, kept_index);
 }
 
 int sba_batch_residual_order_stats(sba_batch* b, int depth_mode, const double* rot, const double* tran, const double* d1,

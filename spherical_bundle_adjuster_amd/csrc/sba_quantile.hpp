@@ -30,6 +30,23 @@ struct SelectState {
   int pad_;
 };
 
+// The device scratch of one selection, carved from the handle's select_scratch: per-pair inlier counts (the residual kernel's
+// by-product) | kept counts | a single problem's two row offsets | ranks | values | scales | thresholds | selection states |
+// histograms | the s plane.
+struct SelectScratch {
+  unsigned long long* n_inlier = nullptr;
+  unsigned long long* kept = nullptr;
+  unsigned long long* offsets = nullptr;
+  unsigned long long* ranks = nullptr;
+  double* values = nullptr;
+  double* scale = nullptr;
+  double* thr = nullptr;
+  SelectState* state = nullptr;
+  unsigned long long* hist = nullptr;
+  double* sq = nullptr;
+  size_t bytes = 0;
+};
+
 // values[g][j] = the ranks[g][j]-th smallest (0-based) of pair g's rows of s, NaN for a pair without rows; with scale != null
 // also thr[g] = scale[g] * values[g][0] (one f64 multiplication).  bpp blocks share a pair.  state [num_pairs] and
 // hist [num_pairs][num_ranks][kSelectBins] are device work space; everything is enqueued on `stream`.

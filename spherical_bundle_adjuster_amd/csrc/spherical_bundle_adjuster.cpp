@@ -227,6 +227,32 @@ int spherical_bundle_adjuster::solve_problem(sba_lm_options& opt, std::vector<cv
                       s2, cov.n_used, cov.n_degenerate);
         }
       }
+      // optional (set_structure_output): what the joint solve leaves behind as structure -- one landmark per match with
+      // its uncertainty score, as an ASCII PLY.  A rank-deficient scene has no covariance, hence no score: reported, no file.
+      if (!structure_path.empty()) {
+        std::vector<double> xyz(3 * static_cast<size_t>(num)), score(static_cast<size_t>(num));
+        sba_joint_cov cov;
+        rc = sba_problem_structure_joint(problem, init_rot, init_tran, &jopt, 0.0, &cov, xyz.data(), nullptr, score.data());
+        if (rc == SBA_ERR_NUMERIC) {
+          std::printf("joint structure: none (%s)\n", sba_last_error());
+        } else if (rc) {
+          return rc;
+        } else {
+          const double s2 = cov.dof > 0 ? 2.0 * cov.cost / cov.dof : 0.0;
+          std::FILE* f = std::fopen(structure_path.c_str(), "w");
+          if (!f) {
+            std::printf("joint structure: cannot write %s\n", structure_path.c_str());
+          } else {
+            std::fprintf(f, "ply\nformat ascii 1.0\ncomment landmarks in the frame of camera 2; q = sigma^2 trace(cov) / |xyz|^2\n"
+                            "element vertex %d\nproperty double x\nproperty double y\nproperty double z\nproperty double q\nend_header\n", num);
+            for (int i = 0; i < num; ++i)
+              std::fprintf(f, "%.17g %.17g %.17g %.17g\n", xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], s2 * score[i]);
+            std::fclose(f);
+            std::printf("joint structure: %d landmarks to %s (sigma^2 = %.6e, %lld degenerate)\n", num, structure_path.c_str(), s2,
+                        cov.n_degenerate);
+          }
+        }
+      }
     }
     return SBA_OK;
   };

@@ -73,6 +73,10 @@ class spherical_bundle_adjuster {
   // With the joint refinement on: one more line after the joint stage, the 1-sigma of rot (degrees) and tran from
   // sba_problem_covariance_joint at the refined pose, scaled by 2 cost / dof.  Nothing else changes.
   void set_joint_covariance(bool on) { joint_covariance = on; }
+  // With the joint refinement on: after the joint stage the triangulated landmarks of sba_problem_structure_joint at the
+  // refined pose go to `path` as an ASCII PLY, one vertex "x y z q" per match in camera 2's frame, q = the uncertainty score
+  // scaled by 2 cost / dof (inf for a degenerate match), and one line reports it.  Empty path: off, nothing else changes.
+  void set_structure_output(const std::string& path) { structure_path = path; }
   // Outlier rejection after the last stage (default off; not in the reference).  The matches whose squared residual norm
   // at the pose and depths reached exceeds scale * (the floor(quantile * (n - 1))-th smallest of those norms) are dropped
   // on the device (sba_problem_keep_below), the same stages run once more on the rest from the pose reached, and one line
@@ -120,6 +124,7 @@ class spherical_bundle_adjuster {
   guess_sampling_t guess_sampling = GUESS_AUTO;
   bool joint_refinement = false;
   bool joint_covariance = false;
+  std::string structure_path;
   double reject_quantile = -1.0, reject_scale = 0.0;   // set_outlier_rejection; off while the quantile is negative
   const void* resident_left = nullptr;   // coordinates currently resident in `problem`
   int resident_n = -1;
