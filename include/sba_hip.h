@@ -650,6 +650,55 @@ int sba_batch_covariance_joint(sba_batch* b, const double* rot, const double* tr
                                double min_sin2_parallax, sba_joint_cov* out /* [num_pairs] */,
                                double* depth_cov /* double[offsets[num_pairs]][3] or NULL */, int* status /* [num_pairs] or NULL */);
 
+/* ---- the batched structure: every pair's triangulated landmarks, their covariances and the cut ---- */
+/* sba_batch_structure_joint: the triangulated structure of the joint problem (sba_problem_structure_joint) for EVERY pair of the
+ * batch.  Pair g gets what sba_problem_structure_joint computes on pair g alone at (rot[g], tran[g]) and the batch's resident
+ * depths, up to the summation order of its Sigma_c: per match the midpoint of the two ray ends in camera 2's frame, its 3 x 3
+ * covariance (xx, yy, zz, xy, xz, yz) under the joint covariance and the score trace / X.X; a degenerate match keeps its xyz and
+ * has the covariance row (+inf, +inf, +inf, 0, 0, 0) and the score +inf.
+ * out: sba_joint_cov[num_pairs] and status (may be NULL): int[num_pairs] -- those of sba_batch_covariance_joint at the same
+ * arguments, bit for bit.  xyz: double[offsets[num_pairs]][3], xyz_cov: double[offsets[num_pairs]][6], score:
+ * double[offsets[num_pairs]], indexed like the uploaded d12 (pair g's match i at row offsets[g] + i; rows below offsets[0] are
+ * not touched); each may be NULL, and an output that is not asked for costs nothing.
+ * Whole-call refusals, decided before a device is touched: those of sba_batch_covariance_joint.
+ * Per pair -- the contract of sba_batch_solve_joint: a pair without a covariance (see sba_batch_covariance_joint) has
+ * status[g] = SBA_ERR_NUMERIC and NaN in every row of every output asked for, xyz included; the call returns SBA_ERR_NUMERIC
+ * when any pair failed, the other pairs' results are valid and the handle stays usable.
+ * Two launches on the batch's stream with no host wait between them: the reduce pass and finish of
+ * sba_batch_covariance_joint (SBA_BATCH_DEVICE_COV=0: its lock-step sequence), then the structure pass over a grid of
+ * (num_pairs, blocks per pair) blocks -- clamp(CUs / num_pairs, 1, 256-vector tiles of the largest pair) blocks per pair,
+ * SBA_BATCH_STRUCTURE_BPP overrides; the bits do not depend on it, nor on the pair layout, nor on the other pairs.  The host
+ * form stages the outputs asked for through a scratch of the handle; the batch (depth planes, scaling state, layout) is not
+ * touched.                                                                                                                    */
+int sba_batch_structure_joint(sba_batch* b, const double* rot, const double* tran, const sba_lm_options* opt,
+                              double min_sin2_parallax, sba_joint_cov* out /* [num_pairs] */, double* xyz, double* xyz_cov,
+                              double* score, int* status /* [num_pairs] or NULL */);
+/* The same with the three destinations in DEVICE memory (the batch's device): arrays of total = offsets[num_pairs] - offsets[0]
+ * rows, the batch's own rows (pair g's match i at row offsets[g] - offsets[0] + i), each 16-byte aligned (else
+ * SBA_ERR_INVALID_ARG and nothing is written) or NULL.  Nothing but out and status crosses to the host.                         */
+int sba_batch_structure_joint_device(sba_batch* b, const double* rot, const double* tran, const sba_lm_options* opt,
+                                     double min_sin2_parallax, sba_joint_cov* out /* [num_pairs] */, double* xyz, double* xyz_cov,
+                                     double* score, int* status /* [num_pairs] or NULL */);
+/* sba_problem_structure_order_stats for every pair: values[g][j] = the ranks[g][j]-th smallest (0-based) of pair g's scores,
+ * bit for bit an element of sba_batch_structure_joint's score rows of that pair; +inf sorts above every finite score.  ranks
+ * and values: [num_pairs][num_ranks], num_ranks 1 ... 8, ranks[g][j] < n[g]; an empty pair takes no part.  A pair without a
+ * covariance has NaN values and status[g] = SBA_ERR_NUMERIC (the call then returns SBA_ERR_NUMERIC, the other pairs' values
+ * are valid).  Refused before a device is touched: what sba_batch_structure_joint refuses (there is no out), NULL ranks /
+ * values, num_ranks out of range, a rank that is not below its pair's size.                                                   */
+int sba_batch_structure_order_stats(sba_batch* b, const double* rot, const double* tran, const sba_lm_options* opt,
+                                    double min_sin2_parallax, const size_t* ranks, int num_ranks, double* values,
+                                    int* status /* [num_pairs] or NULL */);
+/* threshold[g] = scale[g] * q_(rank[g]) of pair g's scores (one IEEE multiplication), then every pair keeps its rows with
+ * score <= threshold[g] through the compaction of sba_batch_compact, whose post-condition holds word for word; degenerate
+ * matches (+inf) stay only under a +inf threshold.  rank, scale, threshold, n_kept: [num_pairs]; kept_index (may be NULL) as
+ * sba_batch_keep_below.  A pair without a covariance is NOT cut: it keeps every row (n_kept[g] = n[g]), its threshold is NaN
+ * and status[g] = SBA_ERR_NUMERIC; the other pairs are cut and the call returns SBA_ERR_NUMERIC -- the handle is then what
+ * sba_batch_compact with that mask leaves.  An empty pair takes no part (NaN, 0).  Refused before a device is touched: what
+ * sba_batch_structure_order_stats refuses, NULL rank / scale / threshold / n_kept, a scale that is not finite or negative.     */
+int sba_batch_structure_keep_below(sba_batch* b, const double* rot, const double* tran, const sba_lm_options* opt,
+                                   double min_sin2_parallax, const size_t* rank, const double* scale, double* threshold,
+                                   size_t* n_kept, long long* kept_index, int* status /* [num_pairs] or NULL */);
+
 /* ---- single matches of a batch: residuals, inlier sets, compaction ---- */
 /* Rows r = 0 .. total - 1 with total = offsets[num_pairs] - offsets[0] of the current layout; row r is the caller's row
  * offsets[0] + r.  rot, tran, d1, d2 as for sba_batch_eval (per pair; NULL depths mean 1.0; ignored with

@@ -182,6 +182,14 @@ SIGNATURES = {
     "sba_batch_solve_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(LmSummary), C.POINTER(C.c_int), _vp]),
     "sba_batch_covariance_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(JointCov), _dp,
                                              C.POINTER(C.c_int)]),
+    "sba_batch_structure_joint": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(JointCov), _dp, _dp, _dp,
+                                            C.POINTER(C.c_int)]),
+    "sba_batch_structure_joint_device": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(JointCov), _vp, _vp,
+                                                   _vp, C.POINTER(C.c_int)]),
+    "sba_batch_structure_order_stats": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(C.c_size_t), C.c_int,
+                                                  _dp, C.POINTER(C.c_int)]),
+    "sba_batch_structure_keep_below": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.POINTER(C.c_size_t), _dp, _dp,
+                                                 C.POINTER(C.c_size_t), _vp, C.POINTER(C.c_int)]),
     "sba_batch_residuals": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _vp, C.POINTER(C.c_size_t)]),
     "sba_batch_compact": (C.c_int, [_vp, _vp, C.POINTER(C.c_size_t), _vp]),
     "sba_batch_keep_inliers": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.POINTER(C.c_size_t), _vp]),

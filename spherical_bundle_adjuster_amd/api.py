@@ -108,6 +108,30 @@ class BatchJointCovariance:
 
 
 @dataclass
+class BatchJointStructure:
+    """Triangulated landmarks of every pair (Batch.structure_joint): JointStructure's arrays for all pairs, rows indexed like
+    the uploaded d12 (pair g's rows are offsets[g] .. offsets[g + 1]).  A pair with status != 0 has no covariance: its rows are
+    NaN in every output, xyz included.  Unscaled: multiply a pair's cov and score by its sigma2."""
+    xyz: np.ndarray | None         # (offsets[-1], 3)
+    cov: np.ndarray | None         # (offsets[-1], 6): xx, yy, zz, xy, xz, yz
+    score: np.ndarray | None       # (offsets[-1],)
+    pose: BatchJointCovariance     # what covariance_joint(depths=False, check=False) returns at the same arguments, bit for bit
+
+    def __getattr__(self, name):
+        """offsets, status, cost, sum_w, n_used, n_degenerate, dim, dof and sigma2 read through to `pose`."""
+        if name in ("offsets", "status", "cost", "sum_w", "n_used", "n_degenerate", "dim", "dof", "sigma2"):
+            return getattr(self.pose, name)
+        raise AttributeError(name)
+
+    def pair(self, g: int) -> JointStructure:
+        """Pair g's slice as the single-problem result type."""
+        g = int(g)
+        lo, hi = int(self.pose.offsets[g]), int(self.pose.offsets[g + 1])
+        cut = lambda a: None if a is None else a[lo:hi]
+        return JointStructure(cut(self.xyz), cut(self.cov), cut(self.score), self.pose.pair(g))
+
+
+@dataclass
 class SolveSummary:
     termination: str
     num_iterations: int
@@ -1087,6 +1111,113 @@ class Batch:
                                     np.array([e.n_used for e in r], dtype=np.int64), np.array([e.n_degenerate for e in r], dtype=np.int64),
                                     np.array([e.dim for e in r], dtype=np.int32), np.array([e.dof for e in r], dtype=np.int32),
                                     status[:B].copy(), np.asarray(self.offsets, dtype=np.int64).copy())
+
+    def _batch_joint_cov(self, res, status) -> BatchJointCovariance:
+        B = self.num_pairs
+        r = res[:B]
+        return BatchJointCovariance(np.array([list(e.cov) for e in r], dtype=np.float64).reshape(B, 6, 6), None,
+                                    np.array([e.cost for e in r], dtype=np.float64), np.array([e.sum_w for e in r], dtype=np.float64),
+                                    np.array([e.n_used for e in r], dtype=np.int64), np.array([e.n_degenerate for e in r], dtype=np.int64),
+                                    np.array([e.dim for e in r], dtype=np.int32), np.array([e.dof for e in r], dtype=np.int32),
+                                    status[:B].copy(), np.asarray(self.offsets, dtype=np.int64).copy())
+
+    def structure_joint(self, rot, tran, options: cabi.LmOptions | None = None, min_sin2_parallax: float = 0.0,
+                        xyz: bool = True, cov: bool = True, score: bool = True, check: bool = True) -> BatchJointStructure:
+        """One 3-D point per match of every pair at (rot[g], tran[g]) and the batch's depths, with its covariance and score
+        (BatchJointStructure): per pair what Problem.structure_joint gives on that pair alone.  xyz / cov / score = False
+        skips that output (it is then None).  A pair without a covariance has status SBA_ERR_NUMERIC and NaN rows; check=True
+        raises SbaError then, check=False returns the result with status, as covariance_joint does.  The batch's state is
+        not touched."""
+        B = self.num_pairs
+        rot = _f64(rot).reshape(B, 3)
+        tran = _f64(tran).reshape(B, 3)
+        res = (cabi.JointCov * max(B, 1))()
+        rows = int(self._total)
+        X = np.zeros((rows, 3)) if xyz else None
+        Cv = np.zeros((rows, 6)) if cov else None
+        q = np.zeros(rows) if score else None
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        ptr = lambda a: None if a is None else _dptr(a)
+        rc = self._lib.sba_batch_structure_joint(self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options),
+                                                 float(min_sin2_parallax), res, ptr(X), ptr(Cv), ptr(q),
+                                                 status.ctypes.data_as(C.POINTER(C.c_int)))
+        if check or rc != cabi.SBA_ERR_NUMERIC:
+            cabi.check(self._lib, rc)
+        return BatchJointStructure(X, Cv, q, self._batch_joint_cov(res, status))
+
+    def structure_joint_into(self, xyz_ptr, cov_ptr, score_ptr, rot, tran, options: cabi.LmOptions | None = None,
+                             min_sin2_parallax: float = 0.0, check: bool = True) -> BatchJointCovariance:
+        """structure_joint with the outputs stored straight into DEVICE memory: xyz_ptr / cov_ptr / score_ptr are device
+        addresses (for example ``tensor.data_ptr()`` of float64 tensors of rows * 3, rows * 6 and rows elements on the
+        batch's device, rows = offsets[-1] - offsets[0], the batch's own rows), 16-byte aligned, 0 or None to skip an output.
+        Returns the pose record; nothing else crosses to the host."""
+        B = self.num_pairs
+        rot = _f64(rot).reshape(B, 3)
+        tran = _f64(tran).reshape(B, 3)
+        res = (cabi.JointCov * max(B, 1))()
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        vp = lambda a: C.c_void_p(int(a)) if a else None
+        rc = self._lib.sba_batch_structure_joint_device(self._h, _dptr(rot), _dptr(tran),
+                                                        None if options is None else C.byref(options), float(min_sin2_parallax),
+                                                        res, vp(xyz_ptr), vp(cov_ptr), vp(score_ptr),
+                                                        status.ctypes.data_as(C.POINTER(C.c_int)))
+        if check or rc != cabi.SBA_ERR_NUMERIC:
+            cabi.check(self._lib, rc)
+        return self._batch_joint_cov(res, status)
+
+    def structure_order_stats(self, rot, tran, ranks, options: cabi.LmOptions | None = None, min_sin2_parallax: float = 0.0,
+                              check: bool = True):
+        """Every pair's ranks[g][j]-th smallest (0-based) of its own structure_joint scores, selected on the device: bit for
+        bit elements of that pair's score rows; inf (degenerate matches) sorts above every finite score.  `ranks`
+        (num_pairs, k), k <= 8, or (k,) for every pair alike.  Returns ((num_pairs, k) values, status (num_pairs,)): NaN
+        values for an empty pair and for a pair without a covariance (status SBA_ERR_NUMERIC; check=True raises then)."""
+        B = self.num_pairs
+        rot = _f64(rot).reshape(B, 3)
+        tran = _f64(tran).reshape(B, 3)
+        r = _ranks(ranks)
+        if r.ndim == 1:
+            r = np.ascontiguousarray(np.broadcast_to(r, (B, r.shape[0])))
+        if r.ndim != 2 or r.shape[0] != B:
+            raise ValueError(f"ranks has shape {r.shape}, the batch holds {B} pairs")
+        vals = np.full((max(B, 1), r.shape[1]), np.nan)
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        rc = self._lib.sba_batch_structure_order_stats(
+            self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options), float(min_sin2_parallax),
+            r.ctypes.data_as(C.POINTER(C.c_size_t)), r.shape[1], _dptr(vals), status.ctypes.data_as(C.POINTER(C.c_int)))
+        if check or rc != cabi.SBA_ERR_NUMERIC:
+            cabi.check(self._lib, rc)
+        return vals[:B], status[:B]
+
+    def structure_keep_below(self, rot, tran, prob, scale, options: cabi.LmOptions | None = None,
+                             min_sin2_parallax: float = 0.0, check: bool = True):
+        """Every pair keeps its rows with score <= scale[g] * (its own `prob` quantile of the scores, rank `quantile_rank` of
+        the pair's size), selected, flagged and compacted on the device as keep_below does; the batch then equals a fresh
+        upload of the kept rows.  Degenerate matches (score inf) go unless the pair's threshold itself is inf.  A pair without
+        a covariance is not cut: it keeps every row, its threshold is NaN and its status SBA_ERR_NUMERIC; check=True raises
+        SbaError then -- AFTER the other pairs were cut, and `offsets` is up to date either way.  `prob` and `scale`: a number
+        or one per pair.  Returns (kept row numbers, the new offsets, the per-pair thresholds, status (num_pairs,))."""
+        B = self.num_pairs
+        rot = _f64(rot).reshape(B, 3)
+        tran = _f64(tran).reshape(B, 3)
+        n = np.diff(self._offsets.astype(np.int64))
+        prob = np.broadcast_to(np.asarray(prob, dtype=np.float64), (B,))
+        rank = np.array([int(quantile_rank(prob[g], int(n[g]))[0]) if n[g] > 0 else 0 for g in range(B)] + [0] * (B == 0),
+                        dtype=np.uintp)
+        sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (max(B, 1),)))
+        thr = np.full(max(B, 1), np.nan)
+        idx = np.empty(max(self._rows(), 1), dtype=np.int64)
+        nk = np.zeros(max(B, 1), dtype=np.uintp)
+        status = np.zeros(max(B, 1), dtype=np.int32)
+        rc = self._lib.sba_batch_structure_keep_below(
+            self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options), float(min_sin2_parallax),
+            rank.ctypes.data_as(C.POINTER(C.c_size_t)), _dptr(sc), _dptr(thr), nk.ctypes.data_as(C.POINTER(C.c_size_t)),
+            idx.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc not in (cabi.SBA_OK, cabi.SBA_ERR_NUMERIC):
+            cabi.check(self._lib, rc)
+        out = (*self._compacted(idx, nk), thr[:B].copy(), status[:B].copy())     # the cut took place: the offsets follow it
+        if check:
+            cabi.check(self._lib, rc)
+        return out
 
     def solve_problem(self, rot=None, tran=None, use_initial_guess: bool = True, trials: int = 80, subset_fraction: float = 0.25,
                       seed: int = 0, options: cabi.LmOptions | None = None, want_depths: bool = False, check: bool = True,

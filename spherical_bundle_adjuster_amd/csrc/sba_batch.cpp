@@ -63,6 +63,8 @@ int free_batch_data(sba_batch* b) {
   b->packs_dev = nullptr; b->packs_host = nullptr; b->packs_host_dev = nullptr;
   if (b->select_scratch) SBA_TRY_HIP(hipFree(b->select_scratch));
   b->select_scratch = nullptr; b->select_scratch_bytes = 0;
+  if (b->structure_scratch) SBA_TRY_HIP(hipFree(b->structure_scratch));
+  b->structure_scratch = nullptr; b->structure_scratch_bytes = 0;
   b->uploaded = false; b->num_pairs = 0; b->n.clear(); b->first_vec.clear();
   return SBA_OK;
 }

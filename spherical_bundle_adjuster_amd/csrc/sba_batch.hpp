@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "sba_internal.hpp"
+#include "sba_quantile.hpp"
 
 struct sba_batch {
   int device = 0;
@@ -85,6 +86,9 @@ struct sba_batch {
   // per-match residuals (sba_batch_residuals, allocated on first use): the per-pair inlier counts, then the outputs
   void* select_scratch = nullptr;
   size_t select_scratch_bytes = 0;
+  // batched structure, host form (sba_batch_structure_joint, grown on demand): the outputs asked for on their way to the host
+  void* structure_scratch = nullptr;
+  size_t structure_scratch_bytes = 0;
 };
 
 namespace sba {
@@ -110,6 +114,33 @@ int ensure_depth_work(sba_batch* b);
 // points, which the batched joint covariance shares (sba_batch_covariance.cpp).
 int joint_check(sba_batch* b, const double* rot, const double* tran);
 void joint_options(const sba_lm_options* opt, sba_lm_options* o);
+
+// sba_batch_covariance.cpp -- the batched covariance's reduce pass and finish, which the batched structure shares
+// (sba_batch_structure.cpp).  cov_enqueue: every pair's record (rot, tran, refused for a non-finite point) and the launches of
+// launch_batch_cov on the batch's stream -- reduce + finish (+ the depth phase into depth_dev, caller row order, when it is not
+// null) in one launch, or with SBA_BATCH_DEVICE_COV=0 the reduce launch, a wait, the host's cov_finish per pair and the depth
+// launch.  cov_wait: until the records of the launch that has not been waited for are on the host.  cov_read: out[g] (may be
+// null) and status[g] (may be null) from the records; returns the number of pairs without a covariance.  cov_failed: that
+// count as the call's return value (SBA_OK or SBA_ERR_NUMERIC with its message).
+struct CovPass {
+  sba_lm_options o;
+  sba::Planes pl;
+  unsigned long long seq = 0;   // what the records' sequence word reaches; 0: nothing is left to wait for
+};
+int cov_enqueue(sba_batch* b, const double* rot, const double* tran, const sba_lm_options* opt, double min_sin2_parallax,
+                double* depth_dev, CovPass* cp);
+int cov_wait(sba_batch* b, CovPass* cp, const char* what);
+int cov_read(const sba_batch* b, sba_joint_cov* out, int* status);
+int cov_failed(int failures, int num_pairs);
+
+// sba_quantile.cpp -- the batch's selection over a plane that is already on the device, in the three steps the single problem
+// has (sba_problem.hpp): the scratch with its plane of batch_rows doubles; ranks (and scales) to the device and the selection;
+// the threshold kernel's keep bytes, the compaction and the thresholds.  grow_scratch: a handle's cached device scratch, grown
+// (or shrunk when far too large) only once the stream has drained.
+int grow_scratch(void** scratch, size_t* have, size_t need, hipStream_t stream, int* poisoned);
+int select_plane(sba_batch* b, int num_ranks, sba::SelectScratch* s, double** plane);
+int select_enqueue(sba_batch* b, const sba::SelectScratch& s, const size_t* ranks, int num_ranks, const double* scale);
+int select_keep(sba_batch* b, const sba::SelectScratch& s, double* threshold, size_t* n_kept, long long* kept_index);
 
 // sba_batch_select.cpp -- what the entry points that look at single matches share (sba_quantile.cpp).
 size_t batch_rows(const sba_batch* b);

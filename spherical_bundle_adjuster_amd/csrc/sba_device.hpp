@@ -490,6 +490,15 @@ hipError_t launch_batch_cov(int store, const Planes& pl, const PairDesc* desc, i
                             double min_sin2, int phases, const unsigned long long* offsets_dev, double* out, BatchCovRec* rec,
                             unsigned int* ticket, unsigned long long* seq_host_dev, unsigned long long seq, hipStream_t stream);
 
+// Batched structure (sba_batch_structure.hip): grid (num_pairs, blocks_per_pair) of 256-thread blocks; follows a
+// kCovReduce | kCovFinish launch of launch_batch_cov on the same stream (or the host's finish) and reads every pair's rot, tran,
+// sigma and dim_status from rec.  xyz [total][3], cov [total][6], score [total]: device pointers in caller row order
+// (offsets_dev relative to the first row), 16-byte aligned, any of them null (that output is compiled out); a pair's own n rows
+// are written, `fill` in every row of a pair whose finish failed.  The bits do not depend on blocks_per_pair.
+hipError_t launch_batch_structure(int store, const Planes& pl, const PairDesc* desc, int num_pairs, int blocks_per_pair,
+                                  const sba_lm_options& opt, double min_sin2, double fill, const unsigned long long* offsets_dev,
+                                  const BatchCovRec* rec, double* xyz, double* cov, double* score, hipStream_t stream);
+
 // 8-point initial guess, device part (.cpp:53-68): A^T A of the kron(left, right) rows for 64 interleaved groups.
 // groups_dev: [64][45]; partials: [grid][45][64] scratch.
 hipError_t launch_epipolar_moments(int store, const Planes& pl, size_t n, double* partials, int grid,

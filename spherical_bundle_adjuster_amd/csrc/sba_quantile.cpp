@@ -164,6 +164,54 @@ int select_keep(sba_problem* p, const SelectScratch& s, double* threshold, size_
 }  // namespace shim
 }  // namespace sba
 
+// ---- the same three steps for a batch (sba_batch.hpp) ------------------------------------------------------------------------
+namespace sba {
+namespace batch {
+
+int grow_scratch(void** scratch, size_t* have, size_t need, hipStream_t stream, int* poisoned) {
+  return ensure_scratch(scratch, have, need, stream, poisoned);
+}
+
+int select_plane(sba_batch* b, int num_ranks, SelectScratch* s, double** plane) {
+  const size_t B = static_cast<size_t>(b->num_pairs), rows = batch_rows(b);
+  const size_t need = carve(nullptr, B, num_ranks, rows).bytes;
+  const int rc = ensure_scratch(&b->select_scratch, &b->select_scratch_bytes, need, b->stream, &b->poisoned);
+  if (rc) return rc;
+  *s = carve(static_cast<char*>(b->select_scratch), B, num_ranks, rows);
+  *plane = s->sq;
+  return SBA_OK;
+}
+
+int select_enqueue(sba_batch* b, const SelectScratch& s, const size_t* ranks, int num_ranks, const double* scale) {
+  const size_t B = static_cast<size_t>(b->num_pairs);
+  SBA_TRY_HIP(hipMemcpyAsync(s.ranks, ranks, B * num_ranks * sizeof(unsigned long long), hipMemcpyHostToDevice, b->stream));
+  if (scale) SBA_TRY_HIP(hipMemcpyAsync(s.scale, scale, B * sizeof(double), hipMemcpyHostToDevice, b->stream));
+  SBA_TRY_HIP(sba::launch_order_stats(s.sq, b->offsets_dev, b->num_pairs, b->bpp, s.ranks, num_ranks, scale ? s.scale : nullptr,
+                                      s.state, s.hist, s.values, s.thr, b->stream));
+  return SBA_OK;
+}
+
+int select_keep(sba_batch* b, const SelectScratch& s, double* threshold, size_t* n_kept, long long* kept_index) {
+  const size_t B = static_cast<size_t>(b->num_pairs);
+  CompactWork w(&b->poisoned);
+  int rc = alloc_work(b, batch_rows(b), &w);
+  if (rc) return rc;
+  SBA_TRY_HIP(sba::launch_keep_below(s.sq, b->offsets_dev, b->num_pairs, b->bpp, s.thr, w.keep, s.kept, b->stream));
+  std::vector<unsigned long long> kept(B);
+  SBA_TRY_HIP(hipMemcpyAsync(threshold, s.thr, B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+  SBA_TRY_HIP(hipMemcpyAsync(kept.data(), s.kept, B * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
+  rc = compact_rows(b, w, n_kept, kept_index);   // waits for the stream before it lays the batch out afresh
+  if (rc) return rc;
+  for (size_t g = 0; g < B; ++g)
+    if (kept[g] != n_kept[g])
+      return sba::set_error(SBA_ERR_NUMERIC, "pair %zu: the threshold kernel kept %llu matches, the compaction %zu", g, kept[g],
+                            n_kept[g]);
+  return SBA_OK;
+}
+
+}  // namespace batch
+}  // namespace sba
+
 namespace {
 
 // ---- batch ---------------------------------------------------------------------------------------------------------------
@@ -180,24 +228,18 @@ int check_batch(const sba_batch* b, int depth_mode, const double* rot, const dou
 
 int enqueue_batch_select(sba_batch* b, int depth_mode, const double* rot, const double* tran, const double* d1,
                          const double* d2, const size_t* ranks, int num_ranks, const double* scale, SelectScratch* out) {
-  const size_t B = static_cast<size_t>(b->num_pairs), rows = sba::batch::batch_rows(b);
-  const size_t need = carve(nullptr, B, num_ranks, rows).bytes;
-  int rc = ensure_scratch(&b->select_scratch, &b->select_scratch_bytes, need, b->stream, &b->poisoned);
+  double* plane = nullptr;
+  int rc = sba::batch::select_plane(b, num_ranks, out, &plane);
   if (rc) return rc;
-  const SelectScratch s = carve(static_cast<char*>(b->select_scratch), B, num_ranks, rows);
-  *out = s;
+  const SelectScratch& s = *out;
   sba::ResidualOut res;
   res.e = nullptr;
-  res.sq = s.sq;
+  res.sq = plane;
   res.inlier = nullptr;
   res.n_inlier = s.n_inlier;
   rc = sba::batch::residual_pass(b, depth_mode, rot, tran, d1, d2, 0.0, 2, res);
   if (rc) return rc;
-  SBA_TRY_HIP(hipMemcpyAsync(s.ranks, ranks, B * num_ranks * sizeof(unsigned long long), hipMemcpyHostToDevice, b->stream));
-  if (scale) SBA_TRY_HIP(hipMemcpyAsync(s.scale, scale, B * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  SBA_TRY_HIP(sba::launch_order_stats(s.sq, b->offsets_dev, b->num_pairs, b->bpp, s.ranks, num_ranks, scale ? s.scale : nullptr,
-                                      s.state, s.hist, s.values, s.thr, b->stream));
-  return SBA_OK;
+  return sba::batch::select_enqueue(b, s, ranks, num_ranks, scale);
 }
 
 }  // namespace
@@ -276,20 +318,7 @@ int sba_batch_keep_below(sba_batch* b, int depth_mode, const double* rot, const 
   SelectScratch s;
   rc = enqueue_batch_select(b, depth_mode, rot, tran, d1, d2, rank, 1, scale, &s);
   if (rc) return rc;
-  sba::batch::CompactWork w(&b->poisoned);
-  rc = sba::batch::alloc_work(b, rows, &w);
-  if (rc) return rc;
-  SBA_TRY_HIP(sba::launch_keep_below(s.sq, b->offsets_dev, b->num_pairs, b->bpp, s.thr, w.keep, s.kept, b->stream));
-  std::vector<unsigned long long> kept(B);
-  SBA_TRY_HIP(hipMemcpyAsync(threshold, s.thr, B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-  SBA_TRY_HIP(hipMemcpyAsync(kept.data(), s.kept, B * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
-  rc = sba::batch::compact_rows(b, w, n_kept, kept_index);   // waits for the stream before it lays the batch out afresh
-  if (rc) return rc;
-  for (size_t g = 0; g < B; ++g)
-    if (kept[g] != n_kept[g])
-      return sba::set_error(SBA_ERR_NUMERIC, "pair %zu: the threshold kernel kept %llu matches, the compaction %zu", g, kept[g],
-                            n_kept[g]);
-  return SBA_OK;
+  return sba::batch::select_keep(b, s, threshold, n_kept, kept_index);
 }
 
 }  // extern "C"
