@@ -13,6 +13,7 @@ long double where the platform has one).  `dense_solve` runs the same accept / r
 import numpy as np
 
 EPS = np.finfo(np.float64).eps
+CANCELLATION_BAND = 1e-4        # |w|^2 below which rotation_derivatives evaluates its closed formula at 50 digits
 TERM = {1: "function", 2: "gradient", 3: "parameter", 4: "no_convergence", 5: "min_radius", 6: "failure"}
 
 DEFAULTS = dict(max_num_iterations=50, initial_trust_region_radius=1e4, max_trust_region_radius=1e16, min_trust_region_radius=1e-32,
@@ -41,8 +42,41 @@ def rotation_derivatives(w, dt=np.float64):
     I = np.eye(3, dtype=dt)
     if th2 <= EPS:
         return [skew(I[j], dt) for j in range(3)]
+    if th2 < CANCELLATION_BAND:
+        return _rotation_derivatives_mp(w, dt)
     R = rotation(w, dt)
     return [(w[j] * skew(w, dt) + skew(np.cross(w, (I - R) @ I[j]), dt)) @ R / th2 for j in range(3)]
+
+
+def _rotation_derivatives_mp(w, dt, digits=50):
+    """The closed formula of rotation_derivatives evaluated at `digits` digits and rounded once to `dt`.  Just above the
+    small-angle threshold I - R is of size |w| and loses its leading digits in `dt`: the quotient by |w|^2 then carries eps / |w|
+    of noise (1e-9 relative at |w| = 3e-8 in float64), far above what the product's series is held to.  Same formula, no
+    series, no left Jacobian -- only the working precision differs."""
+    import mpmath as mp
+    with mp.workdps(digits):
+        def mpf(x):             # exact: a long double is the sum of its float64 head and tail
+            hi = float(x)
+            return mp.mpf(hi) + mp.mpf(float(x - dt(hi)))
+
+        def to_dt(x):
+            return dt(float(x)) if dt == np.float64 else dt(mp.nstr(x, 40))
+
+        def mskew(p):
+            return mp.matrix([[0, -p[2], p[1]], [p[2], 0, -p[0]], [-p[1], p[0], 0]])
+        v = [mpf(x) for x in w]
+        th2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2]
+        th = mp.sqrt(th2)
+        K = mskew(v)
+        Id = mp.eye(3)
+        R = Id + (mp.sin(th) / th) * K + ((1 - mp.cos(th)) / th2) * (K * K)
+        out = []
+        for j in range(3):
+            c = (Id - R)[:, j]
+            cr = [v[1] * c[2] - v[2] * c[1], v[2] * c[0] - v[0] * c[2], v[0] * c[1] - v[1] * c[0]]
+            G = (v[j] * K + mskew(cr)) * R / th2
+            out.append(np.array([[to_dt(G[a, b]) for b in range(3)] for a in range(3)], dtype=dt))
+        return out
 
 
 def huber(delta, s):
