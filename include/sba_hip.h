@@ -18,6 +18,8 @@
  *       -> sba_problem_solve_depths()
  *   - the joint functor over depths, rotation and translation (spherical_bundle_adjuster.cpp:843-889)
  *       -> sba_problem_solve_joint(), sba_problem_eval_joint()
+ *   - (no counterpart in the reference) a further frame registered against the landmarks of a solved pair
+ *       -> sba_problem_solve_resection(), sba_problem_resection_guess()
  *   - pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298)
  *       -> sba_keypoints_to_sphere()
  *   - equi2cube::get_all (equi2cube.cpp:12-302)
@@ -419,6 +421,64 @@ int sba_problem_structure_order_stats(sba_problem* p, const double rot[3], const
 int sba_problem_structure_keep_below(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
                                      double min_sin2_parallax, size_t rank, double scale, double* threshold, size_t* n_kept,
                                      long long* kept_index);
+
+/* ---- spherical resection: a further frame's pose from triangulated landmarks ---------------- */
+/* Registration of a new frame against existing structure.  The handle's LEFT side is the landmark X_i = d1_i x1_i (the
+ * rounded product, as every per-match sweep forms it) in the frame the pose maps from; its RIGHT side y_i = x2_i is the
+ * bearing in the new frame (any length > 0: only its direction counts).  THE d2 COLUMN IS NEVER READ.  The landmarks fix
+ * the scale, so the pose has all six degrees of freedom and no gauge.  Residual as everywhere, the right depth free per
+ * match and eliminated in closed form:
+ *     e_i(rot, tran, d) = d y_i - R(rot) X_i + tran        c_i = -R(rot) X_i + tran
+ *     d_i* = -(y_i . c_i) / (y_i . y_i)                    the minimiser over d (Huber's rho is monotone in |e|^2)
+ *     r_i  = c_i + d_i* y_i = P_i c_i                      P_i = I - y_i y_i^T / (y_i . y_i)
+ *     cost = 1/2 sum rho(|r_i|^2)                          rho = Huber with delta = opt->huber_delta (<= 0: none)
+ * P_i depends on the data only, so d r_i / d (rot, tran) = P_i [A_i | I] exactly, A_i the rotation Jacobian of the explicit
+ * sweep (small-angle handling included), and with w_i = rho' (P idempotent)
+ *     H = sum w_i [A | I]^T P_i [A | I]   (6 x 6 over [rot | tran]),      g = sum w_i [A | I]^T r_i.
+ * One streaming reduction per evaluation (56 B per match with f64 planes), block rows folded in a fixed order: the same
+ * bits on every run.  Once d_i* is stored into the handle's d2 plane (sba_problem_resection_depths) the per-match machinery
+ * sees this very problem: sba_problem_residuals(PER_MATCH) returns r_i, and sba_problem_eval(SBA_MODE_RT, PER_MATCH) at the
+ * same point has the same cost, n_outlier and g (r is perpendicular to y); only H differs, by sum w J^T y^ y^^T J.
+ * n_behind counts the matches with d_i* <= 0 (the landmark lies behind the bearing); they are counted, nothing else.
+ * Refusals, all before the first device call: a poisoned handle and one never uploaded as everywhere; no per-match depths,
+ * a shard, communicator, peer set or all-reduce hook: SBA_ERR_UNSUPPORTED; a non-finite (rot, tran): SBA_ERR_NUMERIC.
+ * Non-finite sums: SBA_ERR_NUMERIC, the handle stays usable.  n == 0 evaluates to zeros.
+ * SBA_RESECT_GRID (read per call): at most this many blocks in the reduce and moments passes (tests).                   */
+typedef struct sba_resection_eq {
+  sba_normal_eq eq;            /* H, g, cost, sum_w, n_outlier as above */
+  double n_behind;
+} sba_resection_eq;
+/* opt (may be NULL: the defaults) is read for huber_delta only. */
+int sba_problem_eval_resection(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
+                               sba_resection_eq* out);
+/* LM over (rot, tran) from the given start: the schedule of sba_problem_solve (SBA_MODE_RT), one reduce pass per
+ * evaluation.  opt == NULL: the defaults, tran_param = SBA_TRAN_FREE (SBA_TRAN_SPHERE is honoured if asked: |tran| stays).
+ * summary and n_behind (at the result) may be NULL.  store_depths != 0: sba_problem_resection_depths at the result.       */
+int sba_problem_solve_resection(sba_problem* p, double rot[3], double tran[3], const sba_lm_options* opt,
+                                sba_lm_summary* summary, double* n_behind, int store_depths);
+/* d_i* at (rot, tran) into the handle's d2 plane (the folded planes are marked stale) and, if d2_out != NULL, to the
+ * host.  No reduction: the bits do not depend on the grid.                                                              */
+int sba_problem_resection_depths(sba_problem* p, const double rot[3], const double tran[3], double* d2_out /* double[n] or NULL */);
+/* Linear starting point (DLT).  y is parallel to M X - tau, so [y]x (M X - tau) = 0 is linear in the 12 entries of
+ * [M | tau]; with X~ = (X, -1) and Q_i = (y . y) I - y y^T the 12 x 12 moment matrix over the column-major vec([M | tau])
+ * is sum (X~ X~^T) (x) Q_i: 60 distinct sums, one streaming pass.  The host takes the eigenvector of the smallest
+ * eigenvalue, the sign with det M > 0, projects M onto SO(3) (scale = mean singular value), tran = tau / scale, and
+ * the rotation vector by a log map that is well-behaved at angle 0 and near pi.  Exact on noise-free data from 6 matches in
+ * general position; NOT robust to outliers: a start for a cut set or a small motion.  info: the eigenvalues lambda1 <=
+ * lambda2 and the largest, lambda12; sv: the three singular values of M over their mean (1, 1, 1 on exact data); n_behind
+ * at the result.  moments (may be NULL): the 60 sums, slot 6 p + q with p the index of (a <= b) in the upper triangle of
+ * X~ X~^T row by row and q that of (c <= d) in Q.  SBA_ERR_NUMERIC (the handle stays usable, rot and tran unwritten):
+ * fewer than 6 matches, a non-finite result, or lambda2 <= 12 * 64 * DBL_EPSILON * lambda12 -- a null space of more than
+ * one dimension at rounding level, such as a planar landmark set (four).  Anything less degenerate is the caller's call.   */
+typedef struct sba_resection_guess_info {
+  double lambda1, lambda2, lambda12;
+  double sv[3];
+  double scale;                /* mean singular value of M: the length of the null vector's rotation part */
+  long long n;
+  double n_behind;
+} sba_resection_guess_info;
+int sba_problem_resection_guess(sba_problem* p, double rot[3], double tran[3], sba_resection_guess_info* info,
+                                double* moments /* double[60] or NULL */);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

@@ -56,6 +56,15 @@ class JointCov(C.Structure):
                 ("n_degenerate", C.c_longlong), ("dim", C.c_int), ("dof", C.c_int)]
 
 
+class ResectionEq(C.Structure):
+    _fields_ = [("eq", NormalEq), ("n_behind", C.c_double)]
+
+
+class ResectionGuessInfo(C.Structure):
+    _fields_ = [("lambda1", C.c_double), ("lambda2", C.c_double), ("lambda12", C.c_double), ("sv", C.c_double * 3),
+                ("scale", C.c_double), ("n", C.c_longlong), ("n_behind", C.c_double)]
+
+
 class LmOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int),
                 ("initial_trust_region_radius", C.c_double),
@@ -140,6 +149,10 @@ SIGNATURES = {
                                                     C.c_int, _dp]),
     "sba_problem_structure_keep_below": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.c_size_t, C.c_double,
                                                    _dp, C.POINTER(C.c_size_t), _vp]),
+    "sba_problem_eval_resection": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(ResectionEq)]),
+    "sba_problem_solve_resection": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(LmSummary), _dp, C.c_int]),
+    "sba_problem_resection_depths": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "sba_problem_resection_guess": (C.c_int, [_vp, _dp, _dp, C.POINTER(ResectionGuessInfo), _dp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

@@ -77,6 +77,33 @@ class JointStructure:
 
 
 @dataclass
+class ResectionEquations:
+    """One reduce pass of the resection (Problem.eval_resection): the six-parameter problem over [rot | tran] with the
+    bearing's depth eliminated per match."""
+    H: np.ndarray          # (6, 6) sum w [A | I]^T P [A | I]
+    g: np.ndarray          # (6,)   sum w [A | I]^T r
+    cost: float            # 1/2 sum rho(|r|^2)
+    sum_w: float
+    n_outlier: float
+    n_behind: float        # matches whose eliminated depth is <= 0 (counted, otherwise treated like any other)
+
+
+@dataclass
+class ResectionGuess:
+    """The linear starting point of the resection (Problem.resection_guess) and what its moment matrix says about it."""
+    rot: np.ndarray        # (3,)
+    tran: np.ndarray       # (3,)
+    lambda1: float         # smallest eigenvalue of the 12 x 12 moment matrix (0 on exact data)
+    lambda2: float         # the next: lambda2 / lambda12 near rounding level = a scene that does not fix the pose
+    lambda12: float        # the largest
+    sv: np.ndarray         # (3,) singular values of the rotation part over their mean: (1, 1, 1) on exact data
+    scale: float
+    n: int
+    n_behind: float        # at (rot, tran)
+    moments: np.ndarray | None   # (60,) the sums, if asked for
+
+
+@dataclass
 class BatchJointCovariance:
     """Covariance of every pair's joint problem (Batch.covariance_joint).  A pair with status != 0 has no covariance: its cov
     and its depth_cov rows are NaN.  Multiply a pair's blocks by its sigma2 for residuals of unknown variance."""
@@ -335,6 +362,14 @@ class Problem:
             dp = d.ctypes.data_as(C.c_void_p)
         cabi.check(self._lib, self._lib.sba_problem_upload(
             self._h, x1.ctypes.data_as(C.c_void_p), x2.ctypes.data_as(C.c_void_p), dp, n, store))
+
+    def upload_landmarks(self, xyz, bearings, store: int = STORE_F64) -> None:
+        """The resection's data: landmarks xyz (n, 3) in the frame the pose maps from and the new frame's bearings (n, 3).
+        Plain `upload` with left = xyz as given and d12 = (1, 1), so the landmark d1 * left is xyz exactly (with STORE_F32 the
+        planes hold xyz rounded to f32).  For landmarks already on the device (structure_joint_into) use upload_device with
+        the rows matched in the new frame as `left` and the caller's own d12, for example ones."""
+        x = _f64(xyz).reshape(-1, 3)
+        self.upload(x, bearings, np.ones((x.shape[0], 2)), store=store)
 
     def upload_keypoints(self, left_kp: np.ndarray, right_kp: np.ndarray, im_width: int, im_height: int, d12=None,
                          store: int = STORE_F64) -> None:
@@ -649,6 +684,51 @@ class Problem:
             self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options), float(min_sin2_parallax), rank,
             float(scale), C.byref(thr), C.byref(kept), idx.ctypes.data_as(C.c_void_p)))
         return idx[:kept.value].copy(), thr.value
+
+    # -- spherical resection: a further frame's pose from landmarks ------------------------------------
+    def eval_resection(self, rot, tran, options: cabi.LmOptions | None = None) -> ResectionEquations:
+        """The resection's normal equations at (rot, tran): landmarks d1 * left, bearings right, the d2 column never read.
+        options is read for huber_delta only (None: the default, 1)."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        eq = cabi.ResectionEq()
+        cabi.check(self._lib, self._lib.sba_problem_eval_resection(self._h, _dptr(rot), _dptr(tran),
+                                                                   None if options is None else C.byref(options), C.byref(eq)))
+        ne = _to_ne(eq.eq)
+        return ResectionEquations(ne.H, ne.g, ne.cost, ne.sum_w, ne.n_outlier, float(eq.n_behind))
+
+    def solve_resection(self, rot, tran, options: cabi.LmOptions | None = None, store_depths: bool = True):
+        """LM over all six pose parameters from (rot, tran), in the scale the landmarks define.  options None = the defaults
+        (tran_param = TRAN_FREE: there is no gauge; TRAN_SPHERE keeps |tran| if asked).  store_depths: the eliminated depths
+        at the result go into the handle's d2 column (resection_depths), after which residuals / keep_below / eval with
+        DEPTH_PER_MATCH see this problem.  Returns (rot, tran, SolveSummary, n_behind); inputs are not modified."""
+        rot = _f64(rot, (3,)).copy()
+        tran = _f64(tran, (3,)).copy()
+        s = cabi.LmSummary()
+        nb = C.c_double(0.0)
+        cabi.check(self._lib, self._lib.sba_problem_solve_resection(self._h, _dptr(rot), _dptr(tran),
+                                                                    None if options is None else C.byref(options), C.byref(s),
+                                                                    C.byref(nb), 1 if store_depths else 0))
+        return rot, tran, _summary(s), float(nb.value)
+
+    def resection_depths(self, rot, tran, return_depths: bool = True):
+        """The eliminated bearing depths d* at (rot, tran) into the handle's d2 column; returns them (n,) or None."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        out = np.zeros(self.size) if return_depths else None
+        cabi.check(self._lib, self._lib.sba_problem_resection_depths(self._h, _dptr(rot), _dptr(tran),
+                                                                     None if out is None else _dptr(out)))
+        return out
+
+    def resection_guess(self, moments: bool = False) -> ResectionGuess:
+        """The linear (DLT) pose from the landmarks and bearings: exact on noise-free data from 6 matches in general position,
+        not robust to outliers.  Raises SbaError(SBA_ERR_NUMERIC) for fewer than 6 matches or a scene that does not fix the
+        pose at rounding level (a planar landmark set); anything less degenerate is the caller's call from lambda2 / lambda12."""
+        rot, tran = np.zeros(3), np.zeros(3)
+        info = cabi.ResectionGuessInfo()
+        mom = np.zeros(60) if moments else None
+        cabi.check(self._lib, self._lib.sba_problem_resection_guess(self._h, _dptr(rot), _dptr(tran), C.byref(info),
+                                                                    None if mom is None else _dptr(mom)))
+        return ResectionGuess(rot, tran, float(info.lambda1), float(info.lambda2), float(info.lambda12),
+                              np.array(info.sv, dtype=np.float64), float(info.scale), int(info.n), float(info.n_behind), mom)
 
     # -- 8-point initial guess ----------------------------------------------------------------------
     def epipolar_moments(self) -> np.ndarray:

@@ -409,6 +409,45 @@ hipError_t launch_joint_step(int store, const Planes& pl, const double* d1, cons
                              const double* sc1, const double* sc2, const JointParams& prm, double* partials, int grid,
                              double* out, double* host_out, unsigned long long seq, hipStream_t stream);
 
+// The fold of [nblocks][JOINT_ROW] block rows into out[count] (count <= 64; slot max_slot, if >= 0, as a maximum) and their
+// publication, for other passes with rows of that stride (sba_resection.hip).
+hipError_t launch_joint_finalize(const double* partials, int nblocks, int count, int max_slot, double* out, double* host_out,
+                                 unsigned long long seq, hipStream_t stream);
+
+// Spherical resection (sba_resection.hip; algebra, row layouts and host finish: sba_resection.hpp).  pl.d2 is never read.
+// ResectParams: the wave-uniform state of a pass, a by-value kernel argument (scalar registers) -- Rn = -R and t as in
+// SweepParams, and the frame of the rotation Jacobian A = -[a]x J (factored_frame) instead of the 27 entries of Gn, which
+// would not fit the scalar registers beside the rest.
+// Reduce: prm.delta > 0 selects the Huber instance, partials [grid][JOINT_ROW],
+// the SBA_RESECT_* slots in out (device) and, with host_out, published as by launch_joint_reduce.  Moments: the
+// SBA_RESECT_MOM_COUNT sums of the linear starting point likewise.  Depths: d_i* into d2 (whole vectors, zeros in the padding).
+struct ResectParams {
+  double Rn[9];
+  double J[9];
+  double t[3];
+  double delta, delta2;     // Huber a and a * a; delta <= 0: no robustifier
+  unsigned long long n;
+  int small_angle;          // rot . rot <= DBL_EPSILON: a = -X, J = I
+  int pad_;
+};
+SBA_HD inline void fill_resect_params(unsigned long long n, const double rot[3], const double tran[3], double huber_delta, ResectParams* prm) {
+  SweepParams sp;
+  fill_sweep_params(n, 1, rot, tran, 1.0, 1.0, huber_delta, &sp, false);
+  double B[9];
+  factored_frame(rot, B, prm->J);
+  for (int i = 0; i < 9; ++i) prm->Rn[i] = sp.Rn[i];
+  for (int i = 0; i < 3; ++i) prm->t[i] = sp.t[i];
+  prm->delta = sp.delta; prm->delta2 = sp.delta2; prm->n = n;
+  prm->small_angle = !(rot[0] * rot[0] + rot[1] * rot[1] + rot[2] * rot[2] > DBL_EPSILON) ? 1 : 0;
+  prm->pad_ = 0;
+}
+hipError_t resect_blocks_per_cu(int store, bool loss, int* blocks);   // resident 256-thread blocks per CU of resect_reduce_kernel
+hipError_t launch_resect_reduce(int store, const Planes& pl, const ResectParams& prm, double* partials, int grid, double* out,
+                                double* host_out, unsigned long long seq, hipStream_t stream);
+hipError_t launch_resect_moments(int store, const Planes& pl, size_t n, double* partials, int grid, double* out, double* host_out,
+                                 unsigned long long seq, hipStream_t stream);
+hipError_t launch_resect_depths(int store, const Planes& pl, const ResectParams& prm, double* d2, int grid, hipStream_t stream);
+
 // Covariance of the joint solve (sba_covariance.hip; algebra and host finish: sba_covariance.hpp).  prm: a first reduce
 // pass's JointParams with inv_radius = 0.  Reduce: partials [grid][COV_ROW], out (device) the COV_OUT_* slots.  Depth:
 // sigma_c the ambient 6 x 6 camera covariance, out [(n + 1) / 2][6] doubles = (var d1, var d2, cov) per match.

@@ -123,6 +123,12 @@ hipError_t launch_joint_reduce(int store, const Planes& pl, const double* d1, co
   return hipGetLastError();
 }
 
+hipError_t launch_joint_finalize(const double* partials, int nblocks, int count, int max_slot, double* out, double* host_out,
+                                 unsigned long long seq, hipStream_t stream) {
+  hipLaunchKernelGGL(joint_finalize_kernel, dim3(1), dim3(1024), 0, stream, partials, nblocks, count, max_slot, out, host_out, seq);
+  return hipGetLastError();
+}
+
 hipError_t launch_joint_step(int store, const Planes& pl, const double* d1, const double* d2, double* c1, double* c2,
                              const double* sc1, const double* sc2, const JointParams& prm, double* partials, int grid,
                              double* out, double* host_out, unsigned long long seq, hipStream_t stream) {

@@ -6,6 +6,7 @@
 //   sba_joint.cpp      joint solve (depths, rotation and translation together) entry points
 //   sba_covariance.cpp covariance of the joint solve at a point (pose 6x6, per-match depth blocks)
 //   sba_structure.cpp  triangulated landmarks with their covariances at a point, and the cut driven by their score
+//   sba_resection.cpp  spherical resection: a further frame's pose from the handle's landmarks d1 x1 and bearings x2
 //   sba_quantile.cpp   order statistics of the per-match squared residual norms and the keep-rule built on them
 // Internal: nothing here is exported from the library.
 #pragma once
@@ -45,6 +46,7 @@ struct sba_problem {
   int joint_occ[2] = {0, 0};       // resident blocks per CU of joint_reduce_kernel per [store]
   int cov_occ[2] = {0, 0};         // ... and of cov_reduce_kernel (sba_covariance.cpp; its rows and outputs share depth_scratch)
   int structure_occ[2] = {0, 0};   // ... and of structure_kernel (sba_structure.cpp; parameters and host-form outputs share depth_scratch)
+  int resect_occ[2][2] = {{0, 0}, {0, 0}};   // ... and of resect_reduce_kernel per [store][loss] (sba_resection.cpp; rows share depth_scratch)
   void* subset_scratch = nullptr;  // reference sampling: [trials][45] moments, then the [trials][m] index lists; kept across calls
   size_t subset_scratch_bytes = 0;
   void* select_scratch = nullptr;  // per-match residuals: inlier count, then the requested outputs; kept across calls
