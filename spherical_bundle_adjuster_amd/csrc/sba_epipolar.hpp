@@ -411,7 +411,8 @@ SBA_HD inline void trial_from_moments(const double* mom45, float e1[3], float e2
 }
 
 // Consensus pick (.cpp:162-180): smallest 20-80 % trimmed mean of the distances to all candidates.
-inline int consensus_pick(const std::vector<Candidate>& c) {
+// avg_out (may be null): the c.size() trimmed means the pick is made from.
+inline int consensus_pick(const std::vector<Candidate>& c, double* avg_out = nullptr) {
   const int r = static_cast<int>(c.size());
   if (r == 0) return -1;
   int best = 0;
@@ -430,6 +431,7 @@ inline int consensus_pick(const std::vector<Candidate>& c) {
     double acc = 0.0;
     for (int j = lo; j < hi; ++j) acc += d[j];
     const double avg = acc / (static_cast<double>(hi - lo) * 1.0);    // 0/0 = NaN for r < 2, as in the reference
+    if (avg_out) avg_out[i] = avg;
     if (i == 0 || avg < best_d) { best = i; best_d = avg; }          // std::min_element keeps the first minimum
   }
   return best;

@@ -29,4 +29,27 @@ int harness_guess_from_trial_moments(const double* moments, int trials, int rows
   for (int i = 0; i < 3; ++i) { euler[i] = r.euler[i]; tran[i] = r.tran[i]; }
   return r.picked;
 }
+// group moments [64][45] -> every candidate of every trial (group_occupancy + group_trial: what thread t of batch_guess_kernel
+// runs), valid or not, in trial order with R1 before R2: euler / tran [2 * trials][3], valid [2 * trials]; avg [2 * trials]:
+// the trimmed means consensus_pick forms, in the order of the valid candidates (the first *ncand entries).
+// Returns the index consensus_pick chooses among the valid candidates (-1: none).
+int harness_guess_candidates(const double* groups, int trials, double fraction, unsigned long long seed, float* euler,
+                             float* tran, int* valid, double* avg, int* ncand) {
+  GroupOccupancy occ;
+  group_occupancy(groups, fraction, &occ);
+  std::vector<Candidate> cand;
+  for (int trial = 0; trial < trials; ++trial) {
+    TrialOut o;
+    group_trial(groups, occ, seed, trial, &o);
+    const Candidate* c[2] = {&o.c1, &o.c2};
+    const bool v[2] = {o.v1, o.v2};
+    for (int k = 0; k < 2; ++k) {
+      for (int i = 0; i < 3; ++i) { euler[3 * (2 * trial + k) + i] = c[k]->euler[i]; tran[3 * (2 * trial + k) + i] = c[k]->tran[i]; }
+      valid[2 * trial + k] = v[k] ? 1 : 0;
+      if (v[k]) cand.push_back(*c[k]);
+    }
+  }
+  *ncand = static_cast<int>(cand.size());
+  return consensus_pick(cand, avg);
+}
 }
