@@ -479,6 +479,52 @@ typedef struct sba_resection_guess_info {
 } sba_resection_guess_info;
 int sba_problem_resection_guess(sba_problem* p, double rot[3], double tran[3], sba_resection_guess_info* info,
                                 double* moments /* double[60] or NULL */);
+/* Candidate poses scored against every match: n_inlier[k] = number of matches with |r_i|^2 <= threshold^2 at candidate k
+ * (r_i as sba_problem_eval_resection forms it; threshold^2 is formed once on the host; a non-finite residual is no inlier).
+ * One streaming pass for all candidates; the counts are sums of integers: the same on every run and for every grid, and
+ * n - n_inlier[k] is sba_problem_eval_resection's n_outlier at huber_delta = threshold.  Refusals, all before the first
+ * device call and with nothing written: a NULL argument: SBA_ERR_INVALID_ARG; the handle refusals of the resection; a
+ * threshold that is not finite and > 0, count outside 1 .. 1024: SBA_ERR_INVALID_ARG; a non-finite candidate:
+ * SBA_ERR_NUMERIC.  n == 0 gives zeros.                                                                                 */
+int sba_problem_score_resection(sba_problem* p, const double* rot /* [count][3] */, const double* tran /* [count][3] */,
+                                int count, double threshold, long long* n_inlier /* [count] */);
+/* Robust starting point: sampled minimal DLT trials, their consensus taken on the device.
+ *   1. Trial t seeds s = seed * 0x2545F4914F6CDD1D + t * 0xD6E8FEB86659FD93 + 1 and draws j = splitmix64(s) % n again and
+ *      again, skipping a j it already holds, until it holds sample_size distinct matches (draw order; host).
+ *   2. One small kernel gathers the sampled rows (X = d1 x1, y) out of the planes; they come back in one copy.
+ *   3. Per trial the 60 DLT moments of its rows in draw order and the finish of sba_problem_resection_guess (host, spread
+ *      over sba_set_host_threads threads; the result does not depend on their number).  A refused finish: the trial is invalid.
+ *   4. Every valid trial's pose is scored as by sba_problem_score_resection, all in one pass.
+ *   5. The largest count wins, the lowest trial index among equals.
+ *   6. refit != 0: the DLT moments over the winner's inliers only (one more streaming pass), the finish, and the refit's
+ *      own score; the refit is returned if its count is >= the winner's, the winner otherwise or if the finish refuses.
+ *   7. n_behind at the returned pose from one reduce pass, as sba_problem_resection_guess has it.
+ * info->refit: lambda1, lambda2, lambda12, sv, scale and n (the inliers refitted) of the refit's finish, zeros if none was
+ * asked for; its n_behind is not filled.  trial_inliers / trial_rot / trial_tran (each may be NULL): every trial's count
+ * (-1: refused) and pose (zeros: refused).  Refusals, all before the first device call and with nothing written: a NULL p,
+ * opt, rot, tran or info: SBA_ERR_INVALID_ARG; the handle refusals of the resection; a threshold that is not finite and
+ * > 0, trials outside 1 .. 1024 or sample_size outside 6 .. 64 (0: the default): SBA_ERR_INVALID_ARG; fewer matches than
+ * sample_size: SBA_ERR_NUMERIC.  No trial finishes (every sample degenerate, e.g. a planar landmark set): SBA_ERR_NUMERIC,
+ * rot / tran unwritten, the handle stays usable.                                                                         */
+typedef struct sba_resection_consensus_options {
+  int trials;                  /* 1 .. 1024; 0 = 128 */
+  int sample_size;             /* 6 .. 64; 0 = 6 */
+  unsigned long long seed;
+  double threshold;            /* > 0, finite; landmark units */
+  int refit;                   /* != 0: linear refit over the best trial's inliers */
+} sba_resection_consensus_options;
+typedef struct sba_resection_consensus_info {
+  long long n, n_inlier;                   /* matches; inliers at the returned pose */
+  long long best_trial, best_trial_inliers;
+  long long n_valid_trials;                /* trials whose DLT finish did not refuse */
+  int refit_used;                          /* the returned pose is the refit */
+  sba_resection_guess_info refit;
+  double n_behind;                         /* at the returned pose */
+} sba_resection_consensus_info;
+int sba_problem_resection_guess_consensus(sba_problem* p, const sba_resection_consensus_options* opt, double rot[3], double tran[3],
+                                          sba_resection_consensus_info* info,
+                                          long long* trial_inliers /* [trials] or NULL; -1 = trial refused */,
+                                          double* trial_rot /* [trials][3] or NULL */, double* trial_tran /* [trials][3] or NULL */);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

@@ -65,6 +65,17 @@ class ResectionGuessInfo(C.Structure):
                 ("scale", C.c_double), ("n", C.c_longlong), ("n_behind", C.c_double)]
 
 
+class ResectionConsensusOptions(C.Structure):
+    _fields_ = [("trials", C.c_int), ("sample_size", C.c_int), ("seed", C.c_ulonglong), ("threshold", C.c_double),
+                ("refit", C.c_int)]
+
+
+class ResectionConsensusInfo(C.Structure):
+    _fields_ = [("n", C.c_longlong), ("n_inlier", C.c_longlong), ("best_trial", C.c_longlong),
+                ("best_trial_inliers", C.c_longlong), ("n_valid_trials", C.c_longlong), ("refit_used", C.c_int),
+                ("refit", ResectionGuessInfo), ("n_behind", C.c_double)]
+
+
 class LmOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int),
                 ("initial_trust_region_radius", C.c_double),
@@ -153,6 +164,9 @@ SIGNATURES = {
     "sba_problem_solve_resection": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(LmSummary), _dp, C.c_int]),
     "sba_problem_resection_depths": (C.c_int, [_vp, _dp, _dp, _dp]),
     "sba_problem_resection_guess": (C.c_int, [_vp, _dp, _dp, C.POINTER(ResectionGuessInfo), _dp]),
+    "sba_problem_score_resection": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
+    "sba_problem_resection_guess_consensus": (C.c_int, [_vp, C.POINTER(ResectionConsensusOptions), _dp, _dp,
+                                                        C.POINTER(ResectionConsensusInfo), C.POINTER(C.c_longlong), _dp, _dp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

@@ -104,6 +104,25 @@ class ResectionGuess:
 
 
 @dataclass
+class ResectionConsensus:
+    """The robust starting point of the resection (Problem.resection_guess_consensus): the best of the sampled DLT trials by
+    its inlier count over all matches, or the linear refit over that trial's inliers."""
+    rot: np.ndarray        # (3,)
+    tran: np.ndarray       # (3,)
+    n: int
+    n_inlier: int          # matches within the threshold at (rot, tran)
+    best_trial: int
+    best_trial_inliers: int
+    n_valid_trials: int    # trials whose DLT finish did not refuse
+    refit_used: bool       # (rot, tran) is the refit, not the best trial itself
+    refit: ResectionGuess | None   # the refit's finish (rot, tran, n_behind and moments not filled: zeros / None); None if not asked for
+    n_behind: float        # at (rot, tran)
+    trial_inliers: np.ndarray | None   # (trials,) int64, -1 = the trial refused; with per_trial
+    trial_rot: np.ndarray | None       # (trials, 3)
+    trial_tran: np.ndarray | None      # (trials, 3)
+
+
+@dataclass
 class BatchJointCovariance:
     """Covariance of every pair's joint problem (Batch.covariance_joint).  A pair with status != 0 has no covariance: its cov
     and its depth_cov rows are NaN.  Multiply a pair's blocks by its sigma2 for residuals of unknown variance."""
@@ -729,6 +748,40 @@ class Problem:
                                                                     None if mom is None else _dptr(mom)))
         return ResectionGuess(rot, tran, float(info.lambda1), float(info.lambda2), float(info.lambda12),
                               np.array(info.sv, dtype=np.float64), float(info.scale), int(info.n), float(info.n_behind), mom)
+
+    def score_resection(self, rots, trans, threshold: float) -> np.ndarray:
+        """For every candidate pose (rots[k], trans[k]), k < count <= 1024, the number of matches whose resection residual has
+        |r| <= threshold: (count,) int64, all candidates in one streaming pass, the same on every run."""
+        rots, trans = np.ascontiguousarray(rots, dtype=np.float64), np.ascontiguousarray(trans, dtype=np.float64)
+        if rots.ndim != 2 or rots.shape[1] != 3 or trans.shape != rots.shape:
+            raise ValueError("rots and trans must both be (count, 3)")
+        out = np.zeros(len(rots), dtype=np.int64)
+        cabi.check(self._lib, self._lib.sba_problem_score_resection(self._h, _dptr(rots), _dptr(trans), len(rots), float(threshold),
+                                                                    out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
+
+    def resection_guess_consensus(self, threshold: float, trials: int = 128, sample_size: int = 6, seed: int = 0,
+                                  refit: bool = True, per_trial: bool = False) -> ResectionConsensus:
+        """A starting pose that survives wrong matches: `trials` DLT trials of `sample_size` sampled matches each, every trial's
+        pose scored against all matches on the device (inliers: |r| <= threshold, landmark units), the best one kept and, with
+        refit, replaced by the DLT over its inliers if that has no fewer.  Raises SbaError(SBA_ERR_NUMERIC) for fewer matches
+        than sample_size or when no trial finishes (every sample degenerate: a planar landmark set)."""
+        opt = cabi.ResectionConsensusOptions(int(trials), int(sample_size), int(seed), float(threshold), 1 if refit else 0)
+        nt = int(trials) if int(trials) > 0 else 128
+        rot, tran = np.zeros(3), np.zeros(3)
+        info = cabi.ResectionConsensusInfo()
+        ti = np.full(max(nt, 1), -1, dtype=np.int64) if per_trial else None
+        tr = np.zeros((max(nt, 1), 3)) if per_trial else None
+        tt = np.zeros((max(nt, 1), 3)) if per_trial else None
+        cabi.check(self._lib, self._lib.sba_problem_resection_guess_consensus(
+            self._h, C.byref(opt), _dptr(rot), _dptr(tran), C.byref(info),
+            None if ti is None else ti.ctypes.data_as(C.POINTER(C.c_longlong)), None if tr is None else _dptr(tr),
+            None if tt is None else _dptr(tt)))
+        g = info.refit
+        fit = ResectionGuess(np.zeros(3), np.zeros(3), float(g.lambda1), float(g.lambda2), float(g.lambda12),
+                             np.array(g.sv, dtype=np.float64), float(g.scale), int(g.n), 0.0, None) if refit else None
+        return ResectionConsensus(rot, tran, int(info.n), int(info.n_inlier), int(info.best_trial), int(info.best_trial_inliers),
+                                  int(info.n_valid_trials), bool(info.refit_used), fit, float(info.n_behind), ti, tr, tt)
 
     # -- 8-point initial guess ----------------------------------------------------------------------
     def epipolar_moments(self) -> np.ndarray:

@@ -448,6 +448,18 @@ hipError_t launch_resect_moments(int store, const Planes& pl, size_t n, double* 
                                  unsigned long long seq, hipStream_t stream);
 hipError_t launch_resect_depths(int store, const Planes& pl, const ResectParams& prm, double* d2, int grid, hipStream_t stream);
 
+// The robust resection guess (sba_resection_consensus.hip; sampler, trial moments and pick: sba_resection_consensus.hpp).
+// Gather: out[rows][6] = (X | y) of the matches index[rows] (each < n), X the rounded product d1 x1 as resect_match forms it.
+// Score: counts[k] (zeroed by the launcher) = matches with |r|^2 <= tau2 at candidate k of table[count][12] = Rn | t
+// (fill_resect_params), 1 <= count <= 1024; integer adds, the same for every grid.  Inlier moments: launch_resect_moments
+// over the matches with |r|^2 <= prm.delta2 at prm only; slot SBA_RESECT_MOM_N is their number.
+hipError_t launch_resect_gather(int store, const Planes& pl, const long long* index, int rows, double* out, hipStream_t stream);
+hipError_t resect_score_blocks_per_cu(int store, int* blocks);   // resident 256-thread blocks per CU of resect_score_kernel
+hipError_t launch_resect_score(int store, const Planes& pl, size_t n, const double* table, int count, double tau2,
+                               unsigned long long* counts, int grid, hipStream_t stream);
+hipError_t launch_resect_inlier_moments(int store, const Planes& pl, const ResectParams& prm, double* partials, int grid, double* out,
+                                        double* host_out, unsigned long long seq, hipStream_t stream);
+
 // Covariance of the joint solve (sba_covariance.hip; algebra and host finish: sba_covariance.hpp).  prm: a first reduce
 // pass's JointParams with inv_radius = 0.  Reduce: partials [grid][COV_ROW], out (device) the COV_OUT_* slots.  Depth:
 // sigma_c the ambient 6 x 6 camera covariance, out [(n + 1) / 2][6] doubles = (var d1, var d2, cov) per match.

@@ -7,6 +7,7 @@
 //   sba_covariance.cpp covariance of the joint solve at a point (pose 6x6, per-match depth blocks)
 //   sba_structure.cpp  triangulated landmarks with their covariances at a point, and the cut driven by their score
 //   sba_resection.cpp  spherical resection: a further frame's pose from the handle's landmarks d1 x1 and bearings x2
+//   sba_resection_consensus.cpp  its robust starting point: sampled DLT trials scored on the device
 //   sba_quantile.cpp   order statistics of the per-match squared residual norms and the keep-rule built on them
 // Internal: nothing here is exported from the library.
 #pragma once
@@ -47,6 +48,9 @@ struct sba_problem {
   int cov_occ[2] = {0, 0};         // ... and of cov_reduce_kernel (sba_covariance.cpp; its rows and outputs share depth_scratch)
   int structure_occ[2] = {0, 0};   // ... and of structure_kernel (sba_structure.cpp; parameters and host-form outputs share depth_scratch)
   int resect_occ[2][2] = {{0, 0}, {0, 0}};   // ... and of resect_reduce_kernel per [store][loss] (sba_resection.cpp; rows share depth_scratch)
+  void* consensus_scratch = nullptr;   // robust resection guess (sba_resection_consensus.cpp): candidate table, counts, sampled indices
+  size_t consensus_scratch_bytes = 0;  // and gathered rows; allocated by the first call, kept across calls
+  int score_occ[2] = {0, 0};           // resident blocks per CU of resect_score_kernel per [store]
   void* subset_scratch = nullptr;  // reference sampling: [trials][45] moments, then the [trials][m] index lists; kept across calls
   size_t subset_scratch_bytes = 0;
   void* select_scratch = nullptr;  // per-match residuals: inlier count, then the requested outputs; kept across calls

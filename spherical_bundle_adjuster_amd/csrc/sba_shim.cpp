@@ -669,6 +669,7 @@ int sba_problem_destroy(sba_problem* p) {
   if (p->peer_sticky) (void)hipFree(p->peer_sticky);
   if (p->epi_scratch) (void)hipFree(p->epi_scratch);
   if (p->subset_scratch) (void)hipFree(p->subset_scratch);
+  if (p->consensus_scratch) (void)hipFree(p->consensus_scratch);
   if (p->select_scratch) (void)hipFree(p->select_scratch);
   if (p->depth_scratch) (void)hipFree(p->depth_scratch);
   if (p->pack_host) (void)hipHostFree(p->pack_host);
