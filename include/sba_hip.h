@@ -20,6 +20,8 @@
  *       -> sba_problem_solve_joint(), sba_problem_eval_joint()
  *   - (no counterpart in the reference) a further frame registered against the landmarks of a solved pair
  *       -> sba_problem_solve_resection(), sba_problem_resection_guess()
+ *          weighted by the landmarks' covariances, with the covariance of the resected pose:
+ *          sba_problem_solve_resection_weighted(), sba_problem_resection_covariance()
  *   - pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298)
  *       -> sba_keypoints_to_sphere()
  *   - equi2cube::get_all (equi2cube.cpp:12-302)
@@ -525,6 +527,67 @@ int sba_problem_resection_guess_consensus(sba_problem* p, const sba_resection_co
                                           sba_resection_consensus_info* info,
                                           long long* trial_inliers /* [trials] or NULL; -1 = trial refused */,
                                           double* trial_rot /* [trials][3] or NULL */, double* trial_tran /* [trials][3] or NULL */);
+
+/* ---- spherical resection weighted by the landmarks' covariances; the pose covariance ---------- */
+/* The resection above with every landmark's 3 x 3 covariance Sigma_i (landmark frame; the row sba_problem_structure_joint
+ * writes: xx, yy, zz, xy, xz, yz) in place of the unit one.  The weights are FROZEN at a reference pose the caller gives:
+ *     S_i = cov_scale R(rot_w) Sigma_i R(rot_w)^T + bearing_sigma^2 d_i*(rot_w, tran_w)^2 (y_i . y_i) I
+ *     M_i = S_i^-1 - S_i^-1 y y^T S_i^-1 / (y^T S_i^-1 y)        the information left once the bearing's depth is eliminated
+ *     s_i = r_i^T M_i r_i                                         from e = d y - R X + t, e ~ N(0, S_i); a chi^2 with 2 d.o.f.
+ *     cost = 1/2 sum rho(s_i)                                     rho = Huber, delta = opt->huber_delta NOW IN SIGMA UNITS
+ *     H = sum w_i [A | I]^T M_i [A | I],   g = sum w_i [A | I]^T M_i r_i,   w_i = rho'(s_i)
+ * M_i y_i = 0: the eliminated depth d_i*, sba_problem_resection_depths and n_behind are those of the unweighted resection.
+ * The weights do not depend on the pose solved for, so g is the exact gradient and H the exact Gauss-Newton matrix.
+ * Zero weight (M_i = 0): a Sigma row with a non-finite entry (the degenerate rows of the structure, NaN), a projected S_i
+ * that is not positive definite (Sigma = 0 with bearing_sigma = 0, a negative variance), a d_i* at the reference that is not
+ * finite.  Such a match adds nothing to any sum (sum_w, n_outlier and n_behind included) and is counted in n_zero_weight,
+ * an integer sum: the same on every run and for every grid.
+ * On the handle: a copy of the Sigma rows (48 B per match) and three f64 planes of the factored weight (24 B per match),
+ * allocated at first use.  EVERY upload and EVERY compaction (sba_problem_compact, _keep_inliers, _keep_below,
+ * _structure_keep_below) drops both: the weighted calls then answer SBA_ERR_UNSUPPORTED until the covariances are set and
+ * frozen again.  Depth rewrites (sba_problem_set_depths, the depth stages, sba_problem_resection_depths) leave them alone.
+ * Refusals of every call below, before the first device call and with nothing written: a NULL argument:
+ * SBA_ERR_INVALID_ARG; the handle refusals of the resection; covariances not set, or (eval / weights / covariance) weights
+ * not frozen: SBA_ERR_UNSUPPORTED.  SBA_RESECT_GRID caps the weighted reduce pass as it caps the unweighted one.           */
+/* cov: 6 n doubles on the host.  cov_scale (finite, > 0, else SBA_ERR_INVALID_ARG) multiplies every row: the place for the
+ * pair's sigma^2 = 2 cost / dof.  Setting covariances discards frozen weights.                                            */
+int sba_problem_resection_set_landmark_cov(sba_problem* p, const double* cov /* double[6 n] */, double cov_scale);
+/* The same from DEVICE memory on the handle's device: 16-byte aligned (else SBA_ERR_INVALID_ARG), copied on the handle's
+ * stream; the call returns once the copy is done.                                                                         */
+int sba_problem_resection_set_landmark_cov_device(sba_problem* p, const void* cov_dev /* double[6 n] */, double cov_scale);
+/* One streaming pass (104 B read, 24 B written per match with f64 planes): the factored weights at (rot_w, tran_w).
+ * bearing_sigma: finite and >= 0, else SBA_ERR_INVALID_ARG; a non-finite pose: SBA_ERR_NUMERIC.  n_zero_weight may be NULL.
+ * No floating-point reduction: the stored bits do not depend on the grid.                                                 */
+int sba_problem_resection_freeze_weights(sba_problem* p, const double rot_w[3], const double tran_w[3], double bearing_sigma,
+                                         long long* n_zero_weight);
+/* The frozen M_i as rows (xx, yy, zz, xy, xz, yz), zeros for a match of zero weight: for inspection and tests. */
+int sba_problem_resection_weights(sba_problem* p, double* info /* double[6 n], host */);
+/* sba_problem_eval_resection with the weights as frozen: one streaming reduction (80 B per match with f64 planes; Sigma is
+ * not read).  The evaluation pose need not be the reference pose.                                                          */
+int sba_problem_eval_resection_weighted(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
+                                        sba_resection_eq* out);
+/* reweight_rounds (1 .. 8, else SBA_ERR_INVALID_ARG) times: freeze at the current pose with bearing_sigma, then the LM of
+ * sba_problem_solve_resection with the weighted evaluator from that pose.  opt == NULL: the defaults, SBA_TRAN_FREE.  summary
+ * (may be NULL) is that of the last round, its seconds_total that of the whole call; n_behind (may be NULL) at the result;
+ * store_depths as sba_problem_solve_resection.  The weights stay frozen where the last round froze them.                  */
+int sba_problem_solve_resection_weighted(sba_problem* p, double rot[3], double tran[3], const sba_lm_options* opt,
+                                         double bearing_sigma, int reweight_rounds, sba_lm_summary* summary, double* n_behind,
+                                         int store_depths);
+/* The covariance of the resected pose: one weighted reduce pass at (rot, tran) with the weights as frozen, then cov = H^-1
+ * by a 6 x 6 Cholesky factorisation on the host.  sigma2 = 2 cost / dof is reported, NOT applied: with honest Sigma_i and
+ * bearing_sigma it is near 1.  dof <= 0, non-finite sums or a failed factorisation: SBA_ERR_NUMERIC, nothing written, the
+ * handle stays usable.  opt (may be NULL: the defaults) is read for huber_delta only.                                    */
+typedef struct sba_resection_cov {
+  double cov[36];              /* over [rot | tran], row-major */
+  double cost, sum_w;
+  long long n_used;            /* n - n_zero_weight */
+  long long n_zero_weight;     /* of the freeze */
+  double n_outlier;
+  long long dof;               /* 2 n_used - 6 */
+  double sigma2;               /* 2 cost / dof */
+} sba_resection_cov;
+int sba_problem_resection_covariance(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
+                                     sba_resection_cov* out);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

@@ -76,6 +76,11 @@ class ResectionConsensusInfo(C.Structure):
                 ("refit", ResectionGuessInfo), ("n_behind", C.c_double)]
 
 
+class ResectionCov(C.Structure):
+    _fields_ = [("cov", C.c_double * 36), ("cost", C.c_double), ("sum_w", C.c_double), ("n_used", C.c_longlong),
+                ("n_zero_weight", C.c_longlong), ("n_outlier", C.c_double), ("dof", C.c_longlong), ("sigma2", C.c_double)]
+
+
 class LmOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int),
                 ("initial_trust_region_radius", C.c_double),
@@ -167,6 +172,14 @@ SIGNATURES = {
     "sba_problem_score_resection": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.POINTER(C.c_longlong)]),
     "sba_problem_resection_guess_consensus": (C.c_int, [_vp, C.POINTER(ResectionConsensusOptions), _dp, _dp,
                                                         C.POINTER(ResectionConsensusInfo), C.POINTER(C.c_longlong), _dp, _dp]),
+    "sba_problem_resection_set_landmark_cov": (C.c_int, [_vp, _dp, C.c_double]),
+    "sba_problem_resection_set_landmark_cov_device": (C.c_int, [_vp, C.c_void_p, C.c_double]),
+    "sba_problem_resection_freeze_weights": (C.c_int, [_vp, _dp, _dp, C.c_double, C.POINTER(C.c_longlong)]),
+    "sba_problem_resection_weights": (C.c_int, [_vp, _dp]),
+    "sba_problem_eval_resection_weighted": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(ResectionEq)]),
+    "sba_problem_solve_resection_weighted": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.c_int,
+                                                       C.POINTER(LmSummary), _dp, C.c_int]),
+    "sba_problem_resection_covariance": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(ResectionCov)]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

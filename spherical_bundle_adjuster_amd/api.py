@@ -89,6 +89,21 @@ class ResectionEquations:
 
 
 @dataclass
+class ResectionCovariance:
+    """The covariance of a resected pose (Problem.resection_covariance): the inverse of the weighted normal matrix at the point,
+    with the weights as frozen.  Not scaled: sigma2 = 2 cost / dof is reported for the caller to judge (near 1 when the landmark
+    covariances and the bearing sigma are honest) or to apply."""
+    cov: np.ndarray        # (6, 6) over [rot | tran]
+    cost: float
+    sum_w: float
+    n_used: int            # n - n_zero_weight
+    n_zero_weight: int     # matches the freeze gave no weight
+    n_outlier: float
+    dof: int               # 2 n_used - 6
+    sigma2: float
+
+
+@dataclass
 class ResectionGuess:
     """The linear starting point of the resection (Problem.resection_guess) and what its moment matrix says about it."""
     rot: np.ndarray        # (3,)
@@ -782,6 +797,70 @@ class Problem:
                              np.array(g.sv, dtype=np.float64), float(g.scale), int(g.n), 0.0, None) if refit else None
         return ResectionConsensus(rot, tran, int(info.n), int(info.n_inlier), int(info.best_trial), int(info.best_trial_inliers),
                                   int(info.n_valid_trials), bool(info.refit_used), fit, float(info.n_behind), ti, tr, tt)
+
+    # -- the resection weighted by the landmarks' covariances ------------------------------------------
+    def set_landmark_covariances(self, cov, scale: float = 1.0) -> None:
+        """One 3 x 3 covariance per landmark, in the landmark frame: (n, 6) rows (xx, yy, zz, xy, xz, yz) as structure_joint
+        returns them; `scale` multiplies every row (the pair's sigma2).  Every upload and compaction drops them again; setting
+        them discards frozen weights."""
+        c = _f64(cov).reshape(-1, 6)
+        if c.shape[0] != self.size:
+            raise ValueError("one covariance row per match")
+        cabi.check(self._lib, self._lib.sba_problem_resection_set_landmark_cov(self._h, _dptr(c), float(scale)))
+
+    def set_landmark_covariances_device(self, ptr, scale: float = 1.0) -> None:
+        """set_landmark_covariances from DEVICE memory: the address of n * 6 float64 on the handle's device (for example
+        ``tensor.data_ptr()``), 16-byte aligned, copied on the handle's stream."""
+        cabi.check(self._lib, self._lib.sba_problem_resection_set_landmark_cov_device(self._h, C.c_void_p(int(ptr) if ptr else 0),
+                                                                                      float(scale)))
+
+    def freeze_resection_weights(self, rot, tran, bearing_sigma: float = 0.0) -> int:
+        """Freeze every match's weight at the reference pose (rot, tran): the landmark covariance rotated into the new frame plus
+        the bearing's noise (bearing_sigma, radians) at the eliminated depth, projected across the bearing.  Returns the number
+        of matches left without weight (non-finite or indefinite covariance, non-finite depth)."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        nz = C.c_longlong(0)
+        cabi.check(self._lib, self._lib.sba_problem_resection_freeze_weights(self._h, _dptr(rot), _dptr(tran), float(bearing_sigma),
+                                                                             C.byref(nz)))
+        return int(nz.value)
+
+    def resection_weights(self) -> np.ndarray:
+        """(n, 6): the frozen information matrix of every match, rows (xx, yy, zz, xy, xz, yz); zeros where the weight is zero."""
+        out = np.zeros((self.size, 6))
+        cabi.check(self._lib, self._lib.sba_problem_resection_weights(self._h, _dptr(out)))
+        return out
+
+    def eval_resection_weighted(self, rot, tran, options: cabi.LmOptions | None = None) -> ResectionEquations:
+        """eval_resection with the frozen weights: cost 1/2 sum rho(r^T M r), huber_delta in sigma units."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        eq = cabi.ResectionEq()
+        cabi.check(self._lib, self._lib.sba_problem_eval_resection_weighted(self._h, _dptr(rot), _dptr(tran),
+                                                                            None if options is None else C.byref(options), C.byref(eq)))
+        ne = _to_ne(eq.eq)
+        return ResectionEquations(ne.H, ne.g, ne.cost, ne.sum_w, ne.n_outlier, float(eq.n_behind))
+
+    def solve_resection_weighted(self, rot, tran, options: cabi.LmOptions | None = None, bearing_sigma: float = 0.0,
+                                 reweight_rounds: int = 1, store_depths: bool = True):
+        """solve_resection with the landmark covariances: `reweight_rounds` (1 .. 8) times freeze the weights at the current pose,
+        then LM from there.  Returns (rot, tran, SolveSummary of the last round, n_behind); the weights stay frozen where the
+        last round froze them, so resection_covariance may follow."""
+        rot = _f64(rot, (3,)).copy()
+        tran = _f64(tran, (3,)).copy()
+        s = cabi.LmSummary()
+        nb = C.c_double(0.0)
+        cabi.check(self._lib, self._lib.sba_problem_solve_resection_weighted(
+            self._h, _dptr(rot), _dptr(tran), None if options is None else C.byref(options), float(bearing_sigma),
+            int(reweight_rounds), C.byref(s), C.byref(nb), 1 if store_depths else 0))
+        return rot, tran, _summary(s), float(nb.value)
+
+    def resection_covariance(self, rot, tran, options: cabi.LmOptions | None = None) -> ResectionCovariance:
+        """The 6 x 6 covariance of the pose at (rot, tran) under the frozen weights (ResectionCovariance)."""
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        res = cabi.ResectionCov()
+        cabi.check(self._lib, self._lib.sba_problem_resection_covariance(self._h, _dptr(rot), _dptr(tran),
+                                                                         None if options is None else C.byref(options), C.byref(res)))
+        return ResectionCovariance(np.array(res.cov, dtype=np.float64).reshape(6, 6), float(res.cost), float(res.sum_w),
+                                   int(res.n_used), int(res.n_zero_weight), float(res.n_outlier), int(res.dof), float(res.sigma2))
 
     # -- 8-point initial guess ----------------------------------------------------------------------
     def epipolar_moments(self) -> np.ndarray:

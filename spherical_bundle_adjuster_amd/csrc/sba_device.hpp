@@ -460,6 +460,28 @@ hipError_t launch_resect_score(int store, const Planes& pl, size_t n, const doub
 hipError_t launch_resect_inlier_moments(int store, const Planes& pl, const ResectParams& prm, double* partials, int grid, double* out,
                                         double* host_out, unsigned long long seq, hipStream_t stream);
 
+// The resection weighted by the landmarks' covariances (sba_resection_weighted.hip; algebra and host finish:
+// sba_resection_weighted.hpp).  ResectWeightParams: the reference pose's ResectParams (delta unused) and the two scalars of
+// S_i, a by-value kernel argument.  ResectWeightPlanes: the three f64 planes of the factored weight, padded to whole
+// 16-byte vectors like the d1 plane.  Freeze: sigma [>= whole vectors of matches][6] (zeros beyond n) -> the planes, whole vectors,
+// zeros in the padding; *n_zero (zeroed by the launcher, device memory) = matches of zero weight, integer adds.  Reduce: the
+// SBA_RESECT_* row exactly as launch_resect_reduce publishes it.  Rows: out [whole vectors of matches][6] = M_i (xx, yy,
+// zz, xy, xz, yz), zeros beyond n.
+struct ResectWeightParams {
+  ResectParams P;
+  double cov_scale, bearing_sigma2;
+};
+struct ResectWeightPlanes {
+  const double* q[3];
+};
+hipError_t resect_wreduce_blocks_per_cu(int store, bool loss, int* blocks);   // resident 256-thread blocks per CU of resect_wreduce_kernel
+hipError_t launch_resect_weights(int store, const Planes& pl, const ResectWeightParams& prm, const double* sigma, double* const q[3],
+                                 unsigned long long* n_zero, int grid, hipStream_t stream);
+hipError_t launch_resect_wreduce(int store, const Planes& pl, const ResectWeightPlanes& wp, const ResectParams& prm, double* partials,
+                                 int grid, double* out, double* host_out, unsigned long long seq, hipStream_t stream);
+hipError_t launch_resect_weight_rows(int store, const Planes& pl, const ResectWeightPlanes& wp, size_t n, double* out, int grid,
+                                     hipStream_t stream);
+
 // Covariance of the joint solve (sba_covariance.hip; algebra and host finish: sba_covariance.hpp).  prm: a first reduce
 // pass's JointParams with inv_radius = 0.  Reduce: partials [grid][COV_ROW], out (device) the COV_OUT_* slots.  Depth:
 // sigma_c the ambient 6 x 6 camera covariance, out [(n + 1) / 2][6] doubles = (var d1, var d2, cov) per match.

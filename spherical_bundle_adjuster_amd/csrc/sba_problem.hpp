@@ -8,6 +8,7 @@
 //   sba_structure.cpp  triangulated landmarks with their covariances at a point, and the cut driven by their score
 //   sba_resection.cpp  spherical resection: a further frame's pose from the handle's landmarks d1 x1 and bearings x2
 //   sba_resection_consensus.cpp  its robust starting point: sampled DLT trials scored on the device
+//   sba_resection_weighted.cpp   the resection weighted by the landmarks' covariances, and the pose covariance
 //   sba_quantile.cpp   order statistics of the per-match squared residual norms and the keep-rule built on them
 // Internal: nothing here is exported from the library.
 #pragma once
@@ -51,6 +52,17 @@ struct sba_problem {
   void* consensus_scratch = nullptr;   // robust resection guess (sba_resection_consensus.cpp): candidate table, counts, sampled indices
   size_t consensus_scratch_bytes = 0;  // and gathered rows; allocated by the first call, kept across calls
   int score_occ[2] = {0, 0};           // resident blocks per CU of resect_score_kernel per [store]
+  // Weighted resection (sba_resection_weighted.cpp), allocated at first use: a copy of the landmark covariance rows
+  // [plane_elems][6] and the three planes of the factored weight [3][plane_elems] followed by the zero-weight counter.
+  // alloc_planes (every upload, every compaction) clears the two flags; the allocations are kept for the next use.
+  double* wres_cov = nullptr;
+  size_t wres_cov_elems = 0;
+  double* wres_planes = nullptr;
+  size_t wres_plane_elems = 0;
+  bool wres_have_cov = false, wres_frozen = false;
+  double wres_cov_scale = 1.0;
+  long long wres_n_zero = 0;               // of the last freeze
+  int wres_occ[2][2] = {{0, 0}, {0, 0}};   // resident blocks per CU of resect_wreduce_kernel per [store][loss]
   void* subset_scratch = nullptr;  // reference sampling: [trials][45] moments, then the [trials][m] index lists; kept across calls
   size_t subset_scratch_bytes = 0;
   void* select_scratch = nullptr;  // per-match residuals: inlier count, then the requested outputs; kept across calls

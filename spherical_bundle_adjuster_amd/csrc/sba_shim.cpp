@@ -288,6 +288,8 @@ int alloc_planes(sba_problem* p, size_t n, bool with_d12, int store) {
   p->uploaded = false;
   p->folded_valid = false;
   p->fold_failed = false;
+  p->wres_have_cov = false;     // n or the row order changes: the weighted resection's covariances and weights are dropped
+  p->wres_frozen = false;
   if (!with_d12 || store != SBA_STORE_F64) {
     const int rc = release_folded(p);
     if (rc) return rc;
@@ -670,6 +672,8 @@ int sba_problem_destroy(sba_problem* p) {
   if (p->epi_scratch) (void)hipFree(p->epi_scratch);
   if (p->subset_scratch) (void)hipFree(p->subset_scratch);
   if (p->consensus_scratch) (void)hipFree(p->consensus_scratch);
+  if (p->wres_cov) (void)hipFree(p->wres_cov);
+  if (p->wres_planes) (void)hipFree(p->wres_planes);
   if (p->select_scratch) (void)hipFree(p->select_scratch);
   if (p->depth_scratch) (void)hipFree(p->depth_scratch);
   if (p->pack_host) (void)hipHostFree(p->pack_host);
