@@ -445,7 +445,7 @@ int sba_problem_structure_keep_below(sba_problem* p, const double rot[3], const 
  * Refusals, all before the first device call: a poisoned handle and one never uploaded as everywhere; no per-match depths,
  * a shard, communicator, peer set or all-reduce hook: SBA_ERR_UNSUPPORTED; a non-finite (rot, tran): SBA_ERR_NUMERIC.
  * Non-finite sums: SBA_ERR_NUMERIC, the handle stays usable.  n == 0 evaluates to zeros.
- * SBA_RESECT_GRID (read per call): at most this many blocks in the reduce and moments passes (tests).                   */
+ * SBA_RESECT_GRID (read per call): at most this many blocks in the reduce, moments and depth passes (tests).            */
 typedef struct sba_resection_eq {
   sba_normal_eq eq;            /* H, g, cost, sum_w, n_outlier as above */
   double n_behind;

@@ -61,7 +61,7 @@ int resect_prepare(sba_problem* p, bool loss, ResectWork* w) {
   if (const char* env = std::getenv("SBA_RESECT_GRID")) { const int v = std::atoi(env); if (v >= 1) cap = v; }
   w->grid = static_cast<int>(std::min<size_t>({blocks, static_cast<size_t>(p->num_cus) * std::min(occ, 2), static_cast<size_t>(cap)}));
   w->moments_grid = static_cast<int>(std::min<size_t>({blocks, static_cast<size_t>(p->num_cus), static_cast<size_t>(cap)}));
-  w->depths_grid = static_cast<int>(std::min<size_t>(blocks, static_cast<size_t>(p->num_cus) * 8));
+  w->depths_grid = static_cast<int>(std::min<size_t>({blocks, static_cast<size_t>(p->num_cus) * 8, static_cast<size_t>(cap)}));
   for (int k = 0; k < 3; ++k) { w->pl.x1[k] = p->coord[k]; w->pl.x2[k] = p->coord[3 + k]; }
   w->pl.d1 = p->dplane[0]; w->pl.d2 = nullptr;     // never read
   return SBA_OK;
