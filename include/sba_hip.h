@@ -22,6 +22,8 @@
  *       -> sba_problem_solve_resection(), sba_problem_resection_guess()
  *          weighted by the landmarks' covariances, with the covariance of the resected pose:
  *          sba_problem_solve_resection_weighted(), sba_problem_resection_covariance()
+ *   - (no counterpart in the reference) the landmarks kept across frames and improved by each registered frame's bearings
+ *       -> sba_landmarks_*()               (a handle of its own; sba_landmarks_fuse: one Kalman update per landmark)
  *   - pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298)
  *       -> sba_keypoints_to_sphere()
  *   - equi2cube::get_all (equi2cube.cpp:12-302)
@@ -588,6 +590,64 @@ typedef struct sba_resection_cov {
 } sba_resection_cov;
 int sba_problem_resection_covariance(sba_problem* p, const double rot[3], const double tran[3], const sba_lm_options* opt,
                                      sba_resection_cov* out);
+
+/* ---- the landmark map: landmarks that live across frames, improved by every registered frame's bearings ---------- */
+/* A handle of its own (the map outlives any one pair or frame): n landmarks X_i with 3 x 3 covariances Sigma_i (landmark
+ * frame; rows xx, yy, zz, xy, xz, yz as sba_problem_structure_joint writes them) and a count of accepted observations per
+ * landmark, as nine f64 planes and one u32 plane on the device, padded to whole 16-byte vectors.  It talks to a problem
+ * handle through device rows only: sba_problem_structure_joint_device -> sba_landmarks_set_device, and sba_landmarks_get_device
+ * -> sba_problem_upload_device (as `left`) + sba_problem_resection_set_landmark_cov_device.
+ * sba_landmarks_fuse is ONE streaming pass: per observation (landmark i, bearing y of any length > 0, from the frame at the
+ * pose (rot, tran) with covariance Sigma_pose over [rot | tran], absent = 0) the exact linear-Gaussian update
+ *     c = -R X + t,  d* = -(y . c) / (y . y),  r = c + d* y                          as the resection forms them
+ *     S = R Sigma R^T + bearing_sigma^2 d*^2 (y . y) I + [A | I] Sigma_pose [A | I]^T
+ *     M = S^-1 - S^-1 y y^T S^-1 / (y^T S^-1 y),   chi2 = r^T M r                    2 degrees of freedom
+ *     X+ = X + Sigma R^T M r,   Sigma+ = Sigma - Sigma R^T M R Sigma
+ * computed through the basis and the Cholesky factor of the weighted resection (csrc/sba_landmarks.hpp).  Every observation
+ * falls into one class, tested in this order: SKIPPED (a non-finite entry of X or Sigma, S not positive definite across
+ * the bearing, a non-finite d* -- a zero bearing --, a non-finite result; chi2 = NaN), BEHIND (d* <= 0), GATED (chi2 >
+ * chi2_gate), FUSED.  Only a fused landmark is rewritten, and its count incremented.  The five counts are integer sums and
+ * there is no floating-point reduction: every result is the same on every run and for every grid (SBA_RESECT_GRID caps it).
+ * The pose term treats the pose as independent of the bearings and of the other landmarks: a pose resected from the same
+ * bearings is correlated with them, and landmarks fused at one pose become correlated with each other; neither is modelled.
+ * Refusals, all before the first device call with nothing written and the handle usable: a NULL argument, a bad option, a
+ * bad idx or m: SBA_ERR_INVALID_ARG; a non-finite pose: SBA_ERR_NUMERIC; a poisoned handle: SBA_ERR_HIP.                  */
+typedef struct sba_landmarks sba_landmarks;
+int sba_landmarks_create(sba_landmarks** out, int device, void* stream /* hipStream_t or NULL: own stream */);
+int sba_landmarks_destroy(sba_landmarks* h);
+int sba_landmarks_size(const sba_landmarks* h, size_t* n);
+/* Replace the map: xyz 3 n and cov 6 n doubles on the host.  cov_scale (finite, > 0) multiplies every covariance row as it
+ * is packed; every observation count becomes 0.  n == 0 empties the map.                                                  */
+int sba_landmarks_set(sba_landmarks* h, const double* xyz /* double[3 n] */, const double* cov /* double[6 n] */, size_t n,
+                      double cov_scale);
+/* The same from DEVICE rows on the handle's device, 16-byte aligned (else SBA_ERR_INVALID_ARG): what
+ * sba_problem_structure_joint_device wrote.  Returns once the rows have been read.                                        */
+int sba_landmarks_set_device(sba_landmarks* h, const void* xyz_dev, const void* cov_dev, size_t n, double cov_scale);
+/* The map as host rows; either array may be NULL. */
+int sba_landmarks_get(sba_landmarks* h, double* xyz /* double[3 n] or NULL */, double* cov /* double[6 n] or NULL */);
+/* The map as rows in the caller's DEVICE memory (16-byte aligned, either may be NULL), exactly n rows each, in the layout
+ * sba_problem_upload_device reads as `left` and sba_problem_resection_set_landmark_cov_device reads.  Complete on return.  */
+int sba_landmarks_get_device(sba_landmarks* h, void* xyz_dev, void* cov_dev);
+/* Accepted observations per landmark since the last set. */
+int sba_landmarks_counts(sba_landmarks* h, uint32_t* out /* [n] */);
+typedef struct sba_landmark_fuse_options {
+  double bearing_sigma;        /* radians; finite and >= 0 */
+  double chi2_gate;            /* > 0; +inf: no gate; NaN or <= 0 is refused */
+  const double* pose_cov;      /* 36 doubles, row-major over [rot | tran] (sba_resection_cov.cov), or NULL: none.  Finite,
+                                  symmetric to the bit, diagonal >= 0 */
+  int apply;                   /* 0: a dry run -- chi2 and counts only, nothing stored */
+} sba_landmark_fuse_options;
+typedef struct sba_landmark_fuse_result {
+  long long n_obs;             /* = n_skipped + n_behind + n_gated + n_fused */
+  long long n_skipped, n_behind, n_gated, n_fused;
+} sba_landmark_fuse_result;
+/* idx == NULL: the dense form, m must equal n, observation j is landmark j and a zero bearing means "not seen" (skipped).
+ * Otherwise observation j is landmark idx[j]: strictly increasing and < n, validated on the host in one pass.  bearings:
+ * 3 m doubles on the host.  chi2_out (m doubles, may be NULL) receives every observation's chi2.  An empty map or m == 0:
+ * zeros and SBA_OK.                                                                                                      */
+int sba_landmarks_fuse(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */, size_t m,
+                       const double rot[3], const double tran[3], const sba_landmark_fuse_options* opt,
+                       sba_landmark_fuse_result* res, double* chi2_out /* [m] or NULL */);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

@@ -81,6 +81,15 @@ class ResectionCov(C.Structure):
                 ("n_zero_weight", C.c_longlong), ("n_outlier", C.c_double), ("dof", C.c_longlong), ("sigma2", C.c_double)]
 
 
+class LandmarkFuseOptions(C.Structure):
+    _fields_ = [("bearing_sigma", C.c_double), ("chi2_gate", C.c_double), ("pose_cov", C.POINTER(C.c_double)), ("apply", C.c_int)]
+
+
+class LandmarkFuseResult(C.Structure):
+    _fields_ = [("n_obs", C.c_longlong), ("n_skipped", C.c_longlong), ("n_behind", C.c_longlong), ("n_gated", C.c_longlong),
+                ("n_fused", C.c_longlong)]
+
+
 class LmOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int),
                 ("initial_trust_region_radius", C.c_double),
@@ -180,6 +189,16 @@ SIGNATURES = {
     "sba_problem_solve_resection_weighted": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.c_double, C.c_int,
                                                        C.POINTER(LmSummary), _dp, C.c_int]),
     "sba_problem_resection_covariance": (C.c_int, [_vp, _dp, _dp, C.POINTER(LmOptions), C.POINTER(ResectionCov)]),
+    "sba_landmarks_create": (C.c_int, [C.POINTER(_vp), C.c_int, _vp]),
+    "sba_landmarks_destroy": (C.c_int, [_vp]),
+    "sba_landmarks_size": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    "sba_landmarks_set": (C.c_int, [_vp, _dp, _dp, C.c_size_t, C.c_double]),
+    "sba_landmarks_set_device": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_double]),
+    "sba_landmarks_get": (C.c_int, [_vp, _dp, _dp]),
+    "sba_landmarks_get_device": (C.c_int, [_vp, _vp, _vp]),
+    "sba_landmarks_counts": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "sba_landmarks_fuse": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp, C.POINTER(LandmarkFuseOptions),
+                                     C.POINTER(LandmarkFuseResult), _dp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

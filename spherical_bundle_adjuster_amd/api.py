@@ -104,6 +104,19 @@ class ResectionCovariance:
 
 
 @dataclass
+class LandmarkFusion:
+    """What one Landmarks.fuse pass did: every observation falls into exactly one class, n_obs = n_skipped + n_behind + n_gated +
+    n_fused.  skipped: a non-finite landmark or covariance, a covariance that is not positive definite across the bearing, a zero
+    bearing, a non-finite result (chi2 is NaN there); behind: the eliminated depth is <= 0; gated: chi2 > chi2_gate."""
+    n_obs: int
+    n_skipped: int
+    n_behind: int
+    n_gated: int
+    n_fused: int
+    chi2: np.ndarray | None    # (m,) per observation, or None when not asked for
+
+
+@dataclass
 class ResectionGuess:
     """The linear starting point of the resection (Problem.resection_guess) and what its moment matrix says about it."""
     rot: np.ndarray        # (3,)
@@ -946,6 +959,106 @@ class Problem:
         p = C.c_void_p()
         cabi.check(self._lib, self._lib.sba_problem_pack_device_ptr(self._h, C.byref(p)))
         return p.value or 0
+
+
+class Landmarks:
+    """A landmark map resident on one GPU (``sba_landmarks``): n landmarks with their 3 x 3 covariances and a count of accepted
+    observations each, kept across frames.  `fuse` folds one registered frame's bearings into them: per landmark the exact
+    linear-Gaussian update of position and covariance from one bearing at a known pose with a known pose covariance."""
+
+    def __init__(self, device: int = 0, stream: int | None = None, lib=None):
+        self._lib = lib if lib is not None else cabi.load_library()
+        self._h = C.c_void_p()
+        cabi.check(self._lib, self._lib.sba_landmarks_create(C.byref(self._h), device, C.c_void_p(stream or 0)))
+        self.device = device
+
+    # -- life cycle ---------------------------------------------------------------------------
+    def close(self) -> None:
+        """Destroy the handle; `destroy_status` keeps the library's answer as Problem.close does (non-zero: POISONED, device
+        resources leaked, the process should exit non-zero)."""
+        if getattr(self, "_h", None) is not None and self._h:
+            self.destroy_status = int(self._lib.sba_landmarks_destroy(self._h))
+            self._h = C.c_void_p()
+            if self.destroy_status != 0:
+                import warnings
+                warnings.warn("sba_landmarks_destroy: " + cabi.last_error(self._lib), ResourceWarning, stacklevel=2)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- data ------------------------------------------------------------------------------------
+    def set(self, xyz, cov, cov_scale: float = 1.0) -> None:
+        """Replace the map: xyz (n, 3) and cov (n, 6) rows (xx, yy, zz, xy, xz, yz) as structure_joint returns them; cov_scale
+        multiplies every covariance row (the pair's sigma2).  Every observation count becomes 0."""
+        x, c = _f64(xyz).reshape(-1, 3), _f64(cov).reshape(-1, 6)
+        if x.shape[0] != c.shape[0]:
+            raise ValueError("one covariance row per landmark")
+        cabi.check(self._lib, self._lib.sba_landmarks_set(self._h, _dptr(x), _dptr(c), x.shape[0], float(cov_scale)))
+
+    def set_device(self, xyz_ptr, cov_ptr, n: int, cov_scale: float = 1.0) -> None:
+        """set from DEVICE rows on the handle's device (for example what Problem.structure_joint_into wrote), 16-byte aligned."""
+        cabi.check(self._lib, self._lib.sba_landmarks_set_device(self._h, C.c_void_p(int(xyz_ptr) if xyz_ptr else 0),
+                                                                 C.c_void_p(int(cov_ptr) if cov_ptr else 0), int(n), float(cov_scale)))
+
+    @property
+    def size(self) -> int:
+        n = C.c_size_t(0)
+        cabi.check(self._lib, self._lib.sba_landmarks_size(self._h, C.byref(n)))
+        return n.value
+
+    def get(self):
+        """(xyz (n, 3), cov (n, 6)): the map as host rows."""
+        n = self.size
+        x, c = np.zeros((n, 3)), np.zeros((n, 6))
+        cabi.check(self._lib, self._lib.sba_landmarks_get(self._h, _dptr(x), _dptr(c)))
+        return x, c
+
+    def get_device(self, xyz_ptr, cov_ptr) -> None:
+        """The map as rows in the caller's DEVICE memory (n * 3 and n * 6 float64, 16-byte aligned, 0 or None to skip one): the
+        layout Problem.upload_device reads as `left` and Problem.set_landmark_covariances_device reads.  Complete on return."""
+        cabi.check(self._lib, self._lib.sba_landmarks_get_device(self._h, C.c_void_p(int(xyz_ptr) if xyz_ptr else 0),
+                                                                 C.c_void_p(int(cov_ptr) if cov_ptr else 0)))
+
+    def counts(self) -> np.ndarray:
+        """(n,) uint32: accepted observations per landmark since the last set."""
+        out = np.zeros(self.size, dtype=np.uint32)
+        cabi.check(self._lib, self._lib.sba_landmarks_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def fuse(self, bearings, rot, tran, bearing_sigma: float = 0.0, chi2_gate: float = float("inf"), pose_cov=None, idx=None,
+             apply: bool = True, want_chi2: bool = True) -> LandmarkFusion:
+        """Fuse one frame's bearings (m, 3), of any length > 0, seen from the pose (rot, tran) with covariance pose_cov (6, 6) over
+        [rot | tran] or None.  idx None: the dense form, one bearing per landmark, a zero bearing = not seen; otherwise observation
+        j is landmark idx[j], strictly increasing.  apply False: a dry run, chi2 and counts only."""
+        y = _f64(bearings).reshape(-1, 3)
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        m = y.shape[0]
+        opt = cabi.LandmarkFuseOptions()
+        opt.bearing_sigma, opt.chi2_gate, opt.apply = float(bearing_sigma), float(chi2_gate), 1 if apply else 0
+        pc = None
+        if pose_cov is not None:
+            pc = _f64(pose_cov, (6, 6))
+            opt.pose_cov = _dptr(pc)
+        ip = None
+        if idx is not None:
+            ii = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+            if ii.shape[0] != m:
+                raise ValueError("one index per bearing")
+            ip = ii.ctypes.data_as(C.POINTER(C.c_int64))
+        chi2 = np.full(m, np.nan) if want_chi2 else None
+        res = cabi.LandmarkFuseResult()
+        cabi.check(self._lib, self._lib.sba_landmarks_fuse(self._h, ip, _dptr(y), m, _dptr(rot), _dptr(tran), C.byref(opt), C.byref(res),
+                                                           None if chi2 is None else _dptr(chi2)))
+        return LandmarkFusion(int(res.n_obs), int(res.n_skipped), int(res.n_behind), int(res.n_gated), int(res.n_fused), chi2)
 
 
 class Batch:

@@ -482,6 +482,26 @@ hipError_t launch_resect_wreduce(int store, const Planes& pl, const ResectWeight
 hipError_t launch_resect_weight_rows(int store, const Planes& pl, const ResectWeightPlanes& wp, size_t n, double* out, int grid,
                                      hipStream_t stream);
 
+// The landmark map (sba_landmarks.hip; the per-observation code and LandmarkFuseParams, a by-value kernel argument:
+// sba_landmarks.hpp).  LandmarkPlanes: ONE allocation of nine f64 planes of `elems` doubles (X.xyz, Sigma xx yy zz xy xz yz) and
+// then one u32 plane of `elems` counts; elems even, zeros beyond n.  Pack: caller rows xyz [n][3], cov [n][6] (device, 16-byte
+// aligned, exactly n rows are read) -> the planes, cov_scale applied, counts and padding zeroed.  Unpack: the reverse, exactly n
+// rows written, either output may be null.  Fuse: idx null = dense (bearings [elems][3], zeros beyond n; chi2 [elems]), else
+// bearings [m][3], chi2 [m] and idx [m] strictly increasing and < n; chi2 may be null; counters: LANDMARK_CLASSES words, zeroed
+// by the launcher.  No floating-point reduction: the bytes do not depend on the grid.
+struct LandmarkFuseParams;
+struct LandmarkPlanes {
+  double* base;
+  size_t elems;
+};
+hipError_t landmarks_fuse_blocks_per_cu(bool indexed, bool apply, int* blocks);   // resident 256-thread blocks per CU of landmarks_fuse_kernel
+hipError_t landmarks_pack_blocks_per_cu(bool unpack, int* blocks);                // ... of landmarks_pack_kernel / landmarks_unpack_kernel
+hipError_t launch_landmarks_pack(const double* xyz, const double* cov, size_t n, double cov_scale, const LandmarkPlanes& pl, int grid,
+                                 hipStream_t stream);
+hipError_t launch_landmarks_unpack(const LandmarkPlanes& pl, size_t n, double* xyz, double* cov, int grid, hipStream_t stream);
+hipError_t launch_landmarks_fuse(const LandmarkPlanes& pl, const LandmarkFuseParams& prm, const long long* idx, const double* bearings,
+                                 double* chi2, unsigned long long* counters, bool apply, int grid, hipStream_t stream);
+
 // Covariance of the joint solve (sba_covariance.hip; algebra and host finish: sba_covariance.hpp).  prm: a first reduce
 // pass's JointParams with inv_radius = 0.  Reduce: partials [grid][COV_ROW], out (device) the COV_OUT_* slots.  Depth:
 // sigma_c the ambient 6 x 6 camera covariance, out [(n + 1) / 2][6] doubles = (var d1, var d2, cov) per match.
