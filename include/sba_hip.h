@@ -23,7 +23,8 @@
  *          weighted by the landmarks' covariances, with the covariance of the resected pose:
  *          sba_problem_solve_resection_weighted(), sba_problem_resection_covariance()
  *   - (no counterpart in the reference) the landmarks kept across frames and improved by each registered frame's bearings
- *       -> sba_landmarks_*()               (a handle of its own; sba_landmarks_fuse: one Kalman update per landmark)
+ *       -> sba_landmarks_*()               (a handle of its own; sba_landmarks_fuse: one Kalman update per landmark;
+ *                                           sba_landmarks_scores / _prune / _append / _gather: the map edited on the device)
  *   - pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298)
  *       -> sba_keypoints_to_sphere()
  *   - equi2cube::get_all (equi2cube.cpp:12-302)
@@ -648,6 +649,51 @@ typedef struct sba_landmark_fuse_result {
 int sba_landmarks_fuse(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */, size_t m,
                        const double rot[3], const double tran[3], const sba_landmark_fuse_options* opt,
                        sba_landmark_fuse_result* res, double* chi2_out /* [m] or NULL */);
+
+/* ---- the landmark map, edited on the device: scores, prune, append, gather ------------------------------------------- */
+/* One turn of incremental mapping without the map leaving the device: sba_landmarks_gather_device the landmarks a frame
+ * matched -> sba_problem_upload_device + sba_problem_resection_set_landmark_cov_device -> resect -> sba_landmarks_fuse ->
+ * sba_landmarks_append_device what the new pair triangulated -> sba_landmarks_prune what stayed bad.  The observation
+ * counts survive every edit; only sba_landmarks_set zeroes them.
+ *   score_i = ((Sigma_xx + Sigma_yy) + Sigma_zz) / ((X.x X.x + X.y X.y) + X.z X.z)      trace Sigma / X . X, as the structure's
+ * in exactly this order in f64 without contraction: float64 arithmetic in the same order gives the same bits.  Nothing is
+ * special-cased: a non-finite input gives a non-finite score, X = 0 gives +inf or NaN.
+ * A prune puts every landmark into one class, tested in this order: INVALID (a non-finite entry of X or Sigma, a negative
+ * variance), UNCERTAIN (!(score <= max_score)), UNOBSERVED (count < min_count), MASKED (mask[i] == 0), KEPT.  With apply the
+ * handle then equals a fresh sba_landmarks_set of the kept rows in their old order with their old counts attached: a stable
+ * compaction into a second plane allocation the handle keeps, after which the two are swapped (a steady prune / append cycle
+ * allocates nothing once both have grown to the map's largest size).  The class counts are integer sums: every result is
+ * the same on every run and for every grid.
+ * Refusals, all before the first device call with nothing written and the handle unchanged and usable: a NULL handle or
+ * required pointer, a bad option, an index out of range, misaligned device rows, a size whose byte counts overflow:
+ * SBA_ERR_INVALID_ARG; a poisoned handle: SBA_ERR_HIP.                                                                     */
+int sba_landmarks_scores(sba_landmarks* h, double* out /* [n] */);
+typedef struct sba_landmark_prune_options {
+  double max_score;            /* >= 0; +inf: no cut; NaN or negative is refused */
+  uint32_t min_count;          /* accepted observations a landmark needs; 0: no cut */
+  const uint8_t* mask;         /* [n] on the host, 0 = drop, or NULL: none */
+  int apply;                   /* 0: a dry run -- the counts and `kept` only, the map unchanged */
+} sba_landmark_prune_options;
+typedef struct sba_landmark_prune_result {
+  long long n_before;          /* = n_invalid + n_uncertain + n_unobserved + n_masked + n_kept */
+  long long n_invalid, n_uncertain, n_unobserved, n_masked, n_kept;
+} sba_landmark_prune_result;
+/* kept (n entries of room, or NULL) receives the old indices of the n_kept kept landmarks, ascending. */
+int sba_landmarks_prune(sba_landmarks* h, const sba_landmark_prune_options* opt, sba_landmark_prune_result* res,
+                        int64_t* kept /* [n] or NULL */);
+/* n_add rows in sba_landmarks_set's layout behind the map's n: the first n landmarks and their counts stay, the new ones
+ * follow with count 0 and cov_scale applied -- as if set had been called with the concatenated rows and the old counts
+ * restored.  n_add == 0 changes nothing; onto an empty map this is set.  The device rows: 16-byte aligned, exactly n_add
+ * of each are read, complete on return.                                                                                   */
+int sba_landmarks_append(sba_landmarks* h, const double* xyz /* double[3 n_add] */, const double* cov /* double[6 n_add] */,
+                         size_t n_add, double cov_scale);
+int sba_landmarks_append_device(sba_landmarks* h, const void* xyz_dev, const void* cov_dev, size_t n_add, double cov_scale);
+/* Rows idx[j] of the map in sba_landmarks_get's row layout, exactly m of each; any output may be NULL.  idx: on the host,
+ * any order, repeats allowed, 0 <= idx[j] < n, validated in one pass.  The device form writes 16-byte aligned DEVICE rows:
+ * what sba_problem_upload_device reads as `left` and sba_problem_resection_set_landmark_cov_device reads.                  */
+int sba_landmarks_gather(sba_landmarks* h, const int64_t* idx /* [m] */, size_t m, double* xyz /* double[3 m] or NULL */,
+                         double* cov /* double[6 m] or NULL */, uint32_t* counts /* [m] or NULL */);
+int sba_landmarks_gather_device(sba_landmarks* h, const int64_t* idx /* [m], host */, size_t m, void* xyz_dev, void* cov_dev);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

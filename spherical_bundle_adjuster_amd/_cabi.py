@@ -90,6 +90,15 @@ class LandmarkFuseResult(C.Structure):
                 ("n_fused", C.c_longlong)]
 
 
+class LandmarkPruneOptions(C.Structure):
+    _fields_ = [("max_score", C.c_double), ("min_count", C.c_uint32), ("mask", C.POINTER(C.c_uint8)), ("apply", C.c_int)]
+
+
+class LandmarkPruneResult(C.Structure):
+    _fields_ = [("n_before", C.c_longlong), ("n_invalid", C.c_longlong), ("n_uncertain", C.c_longlong), ("n_unobserved", C.c_longlong),
+                ("n_masked", C.c_longlong), ("n_kept", C.c_longlong)]
+
+
 class LmOptions(C.Structure):
     _fields_ = [("max_num_iterations", C.c_int),
                 ("initial_trust_region_radius", C.c_double),
@@ -199,6 +208,12 @@ SIGNATURES = {
     "sba_landmarks_counts": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "sba_landmarks_fuse": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp, C.POINTER(LandmarkFuseOptions),
                                      C.POINTER(LandmarkFuseResult), _dp]),
+    "sba_landmarks_scores": (C.c_int, [_vp, _dp]),
+    "sba_landmarks_prune": (C.c_int, [_vp, C.POINTER(LandmarkPruneOptions), C.POINTER(LandmarkPruneResult), C.POINTER(C.c_int64)]),
+    "sba_landmarks_append": (C.c_int, [_vp, _dp, _dp, C.c_size_t, C.c_double]),
+    "sba_landmarks_append_device": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_double]),
+    "sba_landmarks_gather": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_size_t, _dp, _dp, C.POINTER(C.c_uint32)]),
+    "sba_landmarks_gather_device": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_size_t, _vp, _vp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

@@ -117,6 +117,20 @@ class LandmarkFusion:
 
 
 @dataclass
+class LandmarkPrune:
+    """What one Landmarks.prune did: every landmark falls into exactly one class, tested in this order, n_before = n_invalid +
+    n_uncertain + n_unobserved + n_masked + n_kept.  invalid: a non-finite entry of X or Sigma or a negative variance; uncertain:
+    not (score <= max_score); unobserved: count < min_count; masked: the caller's mask is 0 there."""
+    n_before: int
+    n_invalid: int
+    n_uncertain: int
+    n_unobserved: int
+    n_masked: int
+    n_kept: int
+    kept: np.ndarray | None    # (n_kept,) int64, the old indices of the kept landmarks, ascending, or None when not asked for
+
+
+@dataclass
 class ResectionGuess:
     """The linear starting point of the resection (Problem.resection_guess) and what its moment matrix says about it."""
     rot: np.ndarray        # (3,)
@@ -1059,6 +1073,62 @@ class Landmarks:
         cabi.check(self._lib, self._lib.sba_landmarks_fuse(self._h, ip, _dptr(y), m, _dptr(rot), _dptr(tran), C.byref(opt), C.byref(res),
                                                            None if chi2 is None else _dptr(chi2)))
         return LandmarkFusion(int(res.n_obs), int(res.n_skipped), int(res.n_behind), int(res.n_gated), int(res.n_fused), chi2)
+
+    # -- edits: the counts survive all of them -------------------------------------------------------
+    def scores(self) -> np.ndarray:
+        """(n,) trace Sigma / X . X per landmark, ((xx + yy) + zz) / ((x x + y y) + z z) in float64 in exactly that order."""
+        out = np.zeros(self.size)
+        cabi.check(self._lib, self._lib.sba_landmarks_scores(self._h, _dptr(out)))
+        return out
+
+    def prune(self, max_score: float = float("inf"), min_count: int = 0, mask=None, apply: bool = True,
+              want_kept: bool = True) -> LandmarkPrune:
+        """Drop the landmarks that are invalid, whose score exceeds max_score, that have fewer than min_count accepted observations
+        or whose mask entry (n,) is 0; the kept ones close up in their old order with their counts.  apply False: a dry run."""
+        n = self.size
+        opt = cabi.LandmarkPruneOptions()
+        opt.max_score, opt.min_count, opt.apply = float(max_score), int(min_count), 1 if apply else 0
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            if mk.shape[0] != n:
+                raise ValueError("one mask entry per landmark")
+            opt.mask = mk.ctypes.data_as(C.POINTER(C.c_uint8))
+        kept = np.zeros(n, dtype=np.int64) if want_kept else None
+        res = cabi.LandmarkPruneResult()
+        cabi.check(self._lib, self._lib.sba_landmarks_prune(self._h, C.byref(opt), C.byref(res),
+                                                            None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int64))))
+        return LandmarkPrune(int(res.n_before), int(res.n_invalid), int(res.n_uncertain), int(res.n_unobserved), int(res.n_masked),
+                             int(res.n_kept), None if kept is None else kept[:int(res.n_kept)].copy())
+
+    def append(self, xyz, cov, cov_scale: float = 1.0) -> None:
+        """Add rows as `set` takes them behind the map's own: the old landmarks and counts stay, the new ones start at count 0."""
+        x, c = _f64(xyz).reshape(-1, 3), _f64(cov).reshape(-1, 6)
+        if x.shape[0] != c.shape[0]:
+            raise ValueError("one covariance row per landmark")
+        cabi.check(self._lib, self._lib.sba_landmarks_append(self._h, _dptr(x), _dptr(c), x.shape[0], float(cov_scale)))
+
+    def append_device(self, xyz_ptr, cov_ptr, n_add: int, cov_scale: float = 1.0) -> None:
+        """append from DEVICE rows on the handle's device (for example what Problem.structure_joint_into wrote), 16-byte aligned."""
+        cabi.check(self._lib, self._lib.sba_landmarks_append_device(self._h, C.c_void_p(int(xyz_ptr) if xyz_ptr else 0),
+                                                                    C.c_void_p(int(cov_ptr) if cov_ptr else 0), int(n_add), float(cov_scale)))
+
+    def gather(self, idx):
+        """(xyz (m, 3), cov (m, 6), counts (m,)): rows idx of the map; any order, repeats allowed."""
+        ii = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        m = ii.shape[0]
+        x, c, k = np.zeros((m, 3)), np.zeros((m, 6)), np.zeros(m, dtype=np.uint32)
+        cabi.check(self._lib, self._lib.sba_landmarks_gather(self._h, ii.ctypes.data_as(C.POINTER(C.c_int64)), m, _dptr(x), _dptr(c),
+                                                             k.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return x, c, k
+
+    def gather_device(self, idx, xyz_ptr, cov_ptr) -> None:
+        """Rows idx (host indices) of the map as rows in the caller's DEVICE memory (m * 3 and m * 6 float64, 16-byte aligned, 0 or
+        None to skip one): what Problem.upload_device reads as `left` and Problem.set_landmark_covariances_device reads."""
+        ii = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        cabi.check(self._lib, self._lib.sba_landmarks_gather_device(self._h, ii.ctypes.data_as(C.POINTER(C.c_int64)), ii.shape[0],
+                                                                    C.c_void_p(int(xyz_ptr) if xyz_ptr else 0),
+                                                                    C.c_void_p(int(cov_ptr) if cov_ptr else 0)))
 
 
 class Batch:

@@ -502,6 +502,31 @@ hipError_t launch_landmarks_unpack(const LandmarkPlanes& pl, size_t n, double* x
 hipError_t launch_landmarks_fuse(const LandmarkPlanes& pl, const LandmarkFuseParams& prm, const long long* idx, const double* bearings,
                                  double* chi2, unsigned long long* counters, bool apply, int grid, hipStream_t stream);
 
+// Edits of the landmark map (sba_landmarks_edit.hip; the score, the classes of a prune and the checks: sba_landmarks_edit.hpp).
+// Scores: out [elems] doubles (device, 16-byte aligned).  Keep: one streaming pass that writes keep[ntiles * kCompactTile] bytes
+// (1 = kept, 0 beyond n) and adds the LANDMARK_PRUNE_CLASSES class counts to `counters` (zeroed by the launcher):
+// kLandmarkCounterRows rows of kLandmarkCounterStride words, a wave adds to the row its index selects and the caller sums the rows
+// per class -- every wave's atomics on the same five words cost 280 us at 10^7 landmarks (tools/landmark_keep_probe.hip).  mask:
+// device bytes in whole tiles or null.  Scatter: block b = tile b of the compaction (launch_compact_count / _scan give tile_offset);
+// every kept landmark i goes to row tile_offset + rank of dst -- all ten planes, when dst.base is not null -- and i to
+// kept_index (may be null); row n_kept of dst is zeroed when n_kept is odd.  src and dst must not overlap.  Append: dst's
+// n_old + n_add rows = src's first n_old rows with their counts, then the caller's rows (device, exactly n_add of each are
+// read, any 8-byte alignment) with cov_scale applied and count 0; padding zeroed.  Gather: row j of xyz [m][3], cov [m][6],
+// counts [m] (each may be null) = landmark idx[j] < n.  No floating-point reduction: the bytes do not depend on the grid.
+constexpr int kLandmarkCounterRows = 64, kLandmarkCounterStride = 32;   // rows 256 bytes apart
+enum { LANDMARK_EDIT_SCORES = 0, LANDMARK_EDIT_KEEP = 1, LANDMARK_EDIT_APPEND = 2, LANDMARK_EDIT_GATHER = 3, LANDMARK_EDIT_KERNELS = 4 };
+hipError_t landmarks_edit_blocks_per_cu(int which, int* blocks);   // resident 256-thread blocks per CU of the grid-stride kernels
+hipError_t launch_landmarks_scores(const LandmarkPlanes& pl, double* out, int grid, hipStream_t stream);
+hipError_t launch_landmarks_keep(const LandmarkPlanes& pl, size_t n, double max_score, unsigned int min_count, const unsigned char* mask,
+                                 unsigned char* keep, size_t ntiles, unsigned long long* counters, int grid, hipStream_t stream);
+hipError_t launch_landmarks_compact_scatter(const unsigned char* keep, size_t n, const unsigned long long* tile_offset, size_t ntiles,
+                                            const LandmarkPlanes& src, const LandmarkPlanes& dst, size_t n_kept, long long* kept_index,
+                                            hipStream_t stream);
+hipError_t launch_landmarks_append(const LandmarkPlanes& src, size_t n_old, const double* xyz, const double* cov, size_t n_add,
+                                   double cov_scale, const LandmarkPlanes& dst, int grid, hipStream_t stream);
+hipError_t launch_landmarks_gather(const LandmarkPlanes& pl, const long long* idx, size_t m, double* xyz, double* cov, unsigned int* counts,
+                                   int grid, hipStream_t stream);
+
 // Covariance of the joint solve (sba_covariance.hip; algebra and host finish: sba_covariance.hpp).  prm: a first reduce
 // pass's JointParams with inv_radius = 0.  Reduce: partials [grid][COV_ROW], out (device) the COV_OUT_* slots.  Depth:
 // sigma_c the ambient 6 x 6 camera covariance, out [(n + 1) / 2][6] doubles = (var d1, var d2, cov) per match.

@@ -1,7 +1,9 @@
 // Entry points of the landmark map (include/sba_hip.h: sba_landmarks_*): a handle of its own that keeps n landmarks with their
 // 3 x 3 covariances and observation counts on the device as planes, and fuses a registered frame's bearings into them, one
 // streaming pass per frame.  Kernels: sba_landmarks.hip; the per-observation code, the state of a pass and the option and
-// index checks: sba_landmarks.hpp.  Every wait is the bounded stream_wait; a handle whose wait gave up is poisoned.
+// index checks: sba_landmarks.hpp.  Below them the edits of the map -- scores, prune, append, gather -- with their kernels in
+// sba_landmarks_edit.hip and their checks in sba_landmarks_edit.hpp.  Every wait is the bounded stream_wait; a handle whose wait
+// gave up is poisoned.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -11,6 +13,7 @@
 
 #include "sba_internal.hpp"
 #include "sba_landmarks.hpp"
+#include "sba_landmarks_edit.hpp"
 
 struct sba_landmarks {
   int device = 0;
@@ -27,6 +30,13 @@ struct sba_landmarks {
   size_t obs_bytes = 0;
   int occ_fuse[2][2] = {{0, 0}, {0, 0}};   // resident blocks per CU of landmarks_fuse_kernel per [indexed][apply], 0 = unknown
   int occ_pack[2] = {0, 0};                // ... of the pack and the unpack kernel
+  // The edits (scores, prune, append, gather; below sba_landmarks_fuse).  A prune and an append write the other plane allocation
+  // and swap the two: the retired one is kept for the next edit.  edit: the scratch of one edit, kept across calls.
+  double* planes_alt = nullptr;
+  size_t planes_alt_bytes = 0;
+  void* edit = nullptr;
+  size_t edit_bytes = 0;
+  int occ_edit[sba::LANDMARK_EDIT_KERNELS] = {0, 0, 0, 0};
 };
 
 namespace {
@@ -163,6 +173,8 @@ int sba_landmarks_destroy(sba_landmarks* h) {
   }
   if (h->planes) (void)hipFree(h->planes);
   if (h->obs) (void)hipFree(h->obs);
+  if (h->planes_alt) (void)hipFree(h->planes_alt);
+  if (h->edit) (void)hipFree(h->edit);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return SBA_OK;
@@ -247,6 +259,226 @@ int sba_landmarks_fuse(sba_landmarks* h, const int64_t* idx, const double* beari
   res->n_fused = static_cast<long long>(host_counts[sba::LANDMARK_FUSED]);
   res->n_obs = res->n_skipped + res->n_behind + res->n_gated + res->n_fused;
   return SBA_OK;
+}
+
+}  // extern "C"
+
+// ---- the edits: scores, prune, append, gather -------------------------------------------------------------------------------
+namespace {
+
+size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
+
+int edit_occ(sba_landmarks* h, int which, int* occ) {
+  int& o = h->occ_edit[which];
+  if (o == 0) {
+    SBA_TRY_HIP(sba::landmarks_edit_blocks_per_cu(which, &o));
+    o = std::max(1, o);
+  }
+  *occ = o;
+  return SBA_OK;
+}
+
+// The scratch of one edit, at least `bytes`; what it held is lost when it grows.
+int edit_scratch(sba_landmarks* h, size_t bytes) {
+  if (h->edit_bytes >= bytes) return SBA_OK;
+  if (h->edit) SBA_TRY_HIP(hipFree(h->edit));
+  h->edit = nullptr; h->edit_bytes = 0;
+  SBA_TRY_HIP(hipMalloc(&h->edit, bytes));
+  h->edit_bytes = bytes;
+  return SBA_OK;
+}
+
+// The other plane allocation, at least `bytes`: grown only when it is too small, then by half at least.
+int alt_planes(sba_landmarks* h, size_t bytes) {
+  if (h->planes_alt_bytes >= bytes) return SBA_OK;
+  const size_t cap = std::max(bytes, h->planes_alt_bytes + h->planes_alt_bytes / 2);
+  if (h->planes_alt) SBA_TRY_HIP(hipFree(h->planes_alt));
+  h->planes_alt = nullptr; h->planes_alt_bytes = 0;
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&h->planes_alt), cap));
+  h->planes_alt_bytes = cap;
+  return SBA_OK;
+}
+
+// The other allocation holds the map now: n landmarks at a stride of elems.
+void swap_planes(sba_landmarks* h, size_t n, size_t elems) {
+  std::swap(h->planes, h->planes_alt);
+  std::swap(h->planes_bytes, h->planes_alt_bytes);
+  h->n = n; h->elems = elems;
+}
+
+int append_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n_add, double cov_scale, bool from_device) {
+  if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
+  SBA_REFUSE_POISONED(h);
+  if (n_add > 0 && (!xyz || !cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark or covariance array");
+  if (from_device && ((reinterpret_cast<uintptr_t>(xyz) | reinterpret_cast<uintptr_t>(cov)) & 15u))
+    return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
+  if (const char* why = sba::resect_weight_check_scale(cov_scale)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
+  if (const char* why = sba::landmark_check_sizes(h->n, n_add)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (n = %zu, n_add = %zu)", why, h->n, n_add);
+  if (n_add == 0) return SBA_OK;
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  const size_t n_new = h->n + n_add, elems_new = (n_new + 1) / 2 * 2;
+  int rc = alt_planes(h, planes_size(elems_new));
+  if (rc) return rc;
+  const double *xyz_dev = static_cast<const double*>(xyz), *cov_dev = static_cast<const double*>(cov);
+  if (!from_device) {            // covariance rows first: 48 n_add bytes keep the landmark rows 16-byte aligned
+    rc = edit_scratch(h, 9 * n_add * sizeof(double));
+    if (rc) return rc;
+    double* s = static_cast<double*>(h->edit);
+    SBA_TRY_HIP(hipMemcpyAsync(s, cov, 6 * n_add * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    SBA_TRY_HIP(hipMemcpyAsync(s + 6 * n_add, xyz, 3 * n_add * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    cov_dev = s; xyz_dev = s + 6 * n_add;
+  }
+  int occ = 1;
+  rc = edit_occ(h, sba::LANDMARK_EDIT_APPEND, &occ);
+  if (rc) return rc;
+  SBA_TRY_HIP(sba::launch_landmarks_append(planes_of(h), h->n, xyz_dev, cov_dev, n_add, cov_scale, sba::LandmarkPlanes{h->planes_alt, elems_new},
+                                           grid_for(h, elems_new / 2, occ), h->stream));
+  rc = sba::stream_wait(h->stream, "landmark append", &h->poisoned);
+  if (rc) return rc;
+  swap_planes(h, n_new, elems_new);
+  return SBA_OK;
+}
+
+int gather_common(sba_landmarks* h, const int64_t* idx, size_t m, void* xyz, void* cov, uint32_t* counts, bool to_device) {
+  if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
+  SBA_REFUSE_POISONED(h);
+  if (to_device && ((reinterpret_cast<uintptr_t>(xyz) | reinterpret_cast<uintptr_t>(cov)) & 15u))
+    return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
+  if (const char* why = sba::landmark_check_sizes(0, m)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (m = %zu)", why, m);
+  if (const char* why = sba::landmark_check_gather_index(idx, m, h->n)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (m = %zu, n = %zu)", why, m, h->n);
+  if (m == 0 || (!xyz && !cov && !counts)) return SBA_OK;
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  // idx [m] | cov [m][6] | xyz [m][3] | counts [m]: the rows only when they go to the host
+  int rc = edit_scratch(h, m * sizeof(int64_t) + (to_device ? 0 : 9 * m * sizeof(double) + m * sizeof(uint32_t)));
+  if (rc) return rc;
+  static_assert(sizeof(long long) == sizeof(int64_t), "layout of the gather scratch");
+  long long* idx_dev = static_cast<long long*>(h->edit);
+  double *cov_dev = static_cast<double*>(cov), *xyz_dev = static_cast<double*>(xyz);
+  uint32_t* counts_dev = nullptr;
+  if (!to_device) {
+    double* s = reinterpret_cast<double*>(idx_dev + m);
+    cov_dev = cov ? s : nullptr;
+    xyz_dev = xyz ? s + 6 * m : nullptr;
+    counts_dev = counts ? reinterpret_cast<uint32_t*>(s + 9 * m) : nullptr;
+  }
+  SBA_TRY_HIP(hipMemcpyAsync(idx_dev, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  int occ = 1;
+  rc = edit_occ(h, sba::LANDMARK_EDIT_GATHER, &occ);
+  if (rc) return rc;
+  SBA_TRY_HIP(sba::launch_landmarks_gather(planes_of(h), idx_dev, m, xyz_dev, cov_dev, counts_dev, grid_for(h, m, occ), h->stream));
+  if (!to_device) {
+    if (cov) SBA_TRY_HIP(hipMemcpyAsync(cov, cov_dev, 6 * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (xyz) SBA_TRY_HIP(hipMemcpyAsync(xyz, xyz_dev, 3 * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (counts) SBA_TRY_HIP(hipMemcpyAsync(counts, counts_dev, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  }
+  return sba::stream_wait(h->stream, "landmark gather", &h->poisoned);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sba_landmarks_scores(sba_landmarks* h, double* out) {
+  if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
+  SBA_REFUSE_POISONED(h);
+  if (h->n == 0) return SBA_OK;
+  if (!out) return sba::set_error(SBA_ERR_INVALID_ARG, "null output array");
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  int rc = edit_scratch(h, h->elems * sizeof(double));
+  if (rc) return rc;
+  int occ = 1;
+  rc = edit_occ(h, sba::LANDMARK_EDIT_SCORES, &occ);
+  if (rc) return rc;
+  double* scores_dev = static_cast<double*>(h->edit);
+  SBA_TRY_HIP(sba::launch_landmarks_scores(planes_of(h), scores_dev, grid_for(h, h->elems / 2, occ), h->stream));
+  SBA_TRY_HIP(hipMemcpyAsync(out, scores_dev, h->n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return sba::stream_wait(h->stream, "landmark scores", &h->poisoned);
+}
+
+int sba_landmarks_prune(sba_landmarks* h, const sba_landmark_prune_options* opt, sba_landmark_prune_result* res, int64_t* kept) {
+  if (!h || !opt || !res) return sba::set_error(SBA_ERR_INVALID_ARG, "null argument");
+  SBA_REFUSE_POISONED(h);
+  if (const char* why = sba::landmark_check_max_score(opt->max_score)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
+  *res = sba_landmark_prune_result{};
+  res->n_before = static_cast<long long>(h->n);
+  if (h->n == 0) return SBA_OK;
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  // class count rows, total | tile offsets [ntiles] | kept indices [n] | tile counts [ntiles] | keep bytes | mask bytes: whole
+  // tiles of bytes, every part 16-byte aligned
+  const size_t n = h->n, ntiles = (n + sba::kCompactTile - 1) / sba::kCompactTile, tile_bytes = ntiles * sba::kCompactTile;
+  constexpr size_t kCounterWords = static_cast<size_t>(sba::kLandmarkCounterRows) * sba::kLandmarkCounterStride;
+  const size_t o_offset = up16((kCounterWords + 1) * sizeof(unsigned long long));
+  const size_t o_kept = o_offset + up16(ntiles * sizeof(unsigned long long)), o_count = o_kept + up16(n * sizeof(long long));
+  const size_t o_keep = o_count + up16(ntiles * sizeof(unsigned int)), o_mask = o_keep + tile_bytes;
+  int rc = edit_scratch(h, o_mask + tile_bytes);
+  if (rc) return rc;
+  char* s = static_cast<char*>(h->edit);
+  unsigned long long *counters = reinterpret_cast<unsigned long long*>(s), *total = counters + kCounterWords;
+  unsigned long long* tile_offset = reinterpret_cast<unsigned long long*>(s + o_offset);
+  long long* kept_dev = reinterpret_cast<long long*>(s + o_kept);
+  unsigned int* tile_count = reinterpret_cast<unsigned int*>(s + o_count);
+  unsigned char *keep_dev = reinterpret_cast<unsigned char*>(s + o_keep), *mask_dev = reinterpret_cast<unsigned char*>(s + o_mask);
+  static_assert(sizeof(long long) == sizeof(int64_t), "layout of the prune scratch");
+  if (opt->mask) SBA_TRY_HIP(hipMemcpyAsync(mask_dev, opt->mask, n, hipMemcpyHostToDevice, h->stream));
+  int occ = 1;
+  rc = edit_occ(h, sba::LANDMARK_EDIT_KEEP, &occ);
+  if (rc) return rc;
+  SBA_TRY_HIP(sba::launch_landmarks_keep(planes_of(h), n, opt->max_score, opt->min_count, opt->mask ? mask_dev : nullptr, keep_dev, ntiles, counters,
+                                         grid_for(h, tile_bytes / 2, occ), h->stream));
+  const bool apply = opt->apply != 0, scan = apply || kept != nullptr;
+  if (scan) {
+    SBA_TRY_HIP(sba::launch_compact_count(keep_dev, ntiles, tile_count, h->stream));
+    SBA_TRY_HIP(sba::launch_compact_scan(tile_count, ntiles, tile_offset, total, h->stream));
+  }
+  unsigned long long host_rows[kCounterWords + 1] = {0};
+  SBA_TRY_HIP(hipMemcpyAsync(host_rows, counters, (kCounterWords + (scan ? 1 : 0)) * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "landmark keep pass", &h->poisoned);   // the one wait in the middle: the new layout is sized by the kept count
+  if (rc) return rc;
+  unsigned long long host_counts[sba::LANDMARK_PRUNE_CLASSES + 1] = {0, 0, 0, 0, 0, host_rows[kCounterWords]};   // integer sums: any order
+  for (int r = 0; r < sba::kLandmarkCounterRows; ++r)
+    for (int k = 0; k < sba::LANDMARK_PRUNE_CLASSES; ++k) host_counts[k] += host_rows[static_cast<size_t>(r) * sba::kLandmarkCounterStride + k];
+  const size_t n_kept = static_cast<size_t>(host_counts[sba::LANDMARK_KEPT]);
+  if (scan && host_counts[sba::LANDMARK_PRUNE_CLASSES] != n_kept)
+    return sba::set_error(SBA_ERR_NUMERIC, "the keep pass kept %zu landmarks, the compaction %llu", n_kept, host_counts[sba::LANDMARK_PRUNE_CLASSES]);
+  res->n_invalid = static_cast<long long>(host_counts[sba::LANDMARK_INVALID]);
+  res->n_uncertain = static_cast<long long>(host_counts[sba::LANDMARK_UNCERTAIN]);
+  res->n_unobserved = static_cast<long long>(host_counts[sba::LANDMARK_UNOBSERVED]);
+  res->n_masked = static_cast<long long>(host_counts[sba::LANDMARK_MASKED]);
+  res->n_kept = static_cast<long long>(n_kept);
+  if (!scan) return SBA_OK;
+  if (n_kept == 0) {             // an empty map, as set leaves it
+    if (apply) { h->n = 0; h->elems = 0; }
+    return SBA_OK;
+  }
+  const size_t elems_new = (n_kept + 1) / 2 * 2;
+  sba::LandmarkPlanes dst{nullptr, 0};
+  if (apply) {
+    rc = alt_planes(h, planes_size(elems_new));
+    if (rc) return rc;
+    dst = sba::LandmarkPlanes{h->planes_alt, elems_new};
+  }
+  SBA_TRY_HIP(sba::launch_landmarks_compact_scatter(keep_dev, n, tile_offset, ntiles, planes_of(h), dst, n_kept, kept ? kept_dev : nullptr, h->stream));
+  if (kept) SBA_TRY_HIP(hipMemcpyAsync(kept, kept_dev, n_kept * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "landmark compaction", &h->poisoned);
+  if (rc) return rc;
+  if (apply) swap_planes(h, n_kept, elems_new);
+  return SBA_OK;
+}
+
+int sba_landmarks_append(sba_landmarks* h, const double* xyz, const double* cov, size_t n_add, double cov_scale) {
+  return append_common(h, xyz, cov, n_add, cov_scale, false);
+}
+
+int sba_landmarks_append_device(sba_landmarks* h, const void* xyz_dev, const void* cov_dev, size_t n_add, double cov_scale) {
+  return append_common(h, xyz_dev, cov_dev, n_add, cov_scale, true);
+}
+
+int sba_landmarks_gather(sba_landmarks* h, const int64_t* idx, size_t m, double* xyz, double* cov, uint32_t* counts) {
+  return gather_common(h, idx, m, xyz, cov, counts, false);
+}
+
+int sba_landmarks_gather_device(sba_landmarks* h, const int64_t* idx, size_t m, void* xyz_dev, void* cov_dev) {
+  return gather_common(h, idx, m, xyz_dev, cov_dev, nullptr, true);
 }
 
 }  // extern "C"

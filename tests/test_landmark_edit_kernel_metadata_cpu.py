@@ -1,0 +1,68 @@
+"""CPU: the code-object METADATA of the kernels that edit the landmark map (csrc/sba_landmarks_edit.hip compiled for gfx950 with
+the Makefile's flags; hipcc cross-compiles): the scores, keep, compact-scatter, append and gather kernels exist and no others, none
+uses scratch memory or spills a vector register, blocks are 256 threads, and every one of them fits at least two blocks per CU, as
+DESIGN.md section 3.21 states.  Only the .amdgpu_metadata records are read."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "spherical_bundle_adjuster_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+pytestmark = pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not available")
+
+REGISTER_FILE = 512      # unified vector registers per lane of a gfx950 SIMD (vector + accumulation registers)
+GRANULE = 8              # allocation granularity
+KERNELS = ("landmarks_scores_kernel", "landmarks_keep_kernel", "landmarks_compact_scatter_kernel", "landmarks_append_kernel",
+           "landmarks_gather_kernel")
+
+
+@pytest.fixture(scope="module")
+def metadata(tmp_path_factory):
+    """kernel name -> {field: int} from the .amdgpu_metadata records."""
+    flags = subprocess.run(["make", "-s", "-C", CSRC, "print-flags"], check=True, capture_output=True, text=True).stdout.split()
+    out = tmp_path_factory.mktemp("landmark_edit_meta") / "sba_landmarks_edit.s"
+    hipcc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
+    subprocess.run([hipcc, *flags, "-S", "--cuda-device-only", os.path.join(CSRC, "sba_landmarks_edit.hip"), "-o", str(out)],
+                   check=True, capture_output=True, cwd=CSRC)
+    text = out.read_text()
+    meta = text[text.index(".amdgpu_metadata"):text.index(".end_amdgpu_metadata")]
+    kernels = {}
+    for rec in meta.split("  - .agpr_count:")[1:]:
+        rec = ".agpr_count:" + rec
+        fields = dict(re.findall(r"\.(\w+):\s+(\S+)", rec))
+        kernels[fields["name"]] = {k: int(v) for k, v in fields.items() if re.fullmatch(r"\d+", v)}
+    return kernels
+
+
+def _blocks_per_cu(f):
+    regs = -(-(f["vgpr_count"] + f["agpr_count"]) // GRANULE) * GRANULE
+    return REGISTER_FILE // regs
+
+
+def test_the_expected_kernels_and_no_others(metadata):
+    assert len(metadata) == len(KERNELS), list(metadata)
+    for name in KERNELS:
+        assert sum(name in k for k in metadata) == 1, (name, list(metadata))
+
+
+def test_the_makefile_builds_the_file():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    srcs = re.search(r"^SRCS_HIP := (.*)$", mk, flags=re.M).group(1).split()
+    assert "sba_landmarks_edit.hip" in srcs and "sba_landmarks.hip" in srcs
+
+
+def test_no_scratch_no_vector_spills_and_two_blocks_fit(metadata):
+    """A 256-thread block is one wave per SIMD: b blocks per CU need b register sets in the 512-entry file."""
+    for k, f in sorted(metadata.items()):
+        print(f"{k}: {f['vgpr_count']} vector + {f['agpr_count']} accumulation registers, {f['sgpr_count']} scalar "
+              f"({f['sgpr_spill_count']} parked in vector lanes), {f['group_segment_fixed_size']} B LDS, "
+              f"{f['kernarg_segment_size']} B arguments, {_blocks_per_cu(f)} block(s) per CU")
+        assert f["private_segment_fixed_size"] == 0, (k, f)
+        assert f["vgpr_spill_count"] == 0, (k, f)
+        assert f["max_flat_workgroup_size"] == 256, (k, f)
+        assert _blocks_per_cu(f) >= 2, (k, f)
