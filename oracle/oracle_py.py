@@ -104,6 +104,31 @@ def point(mode, cam1, cam2, rot, tran, d1, d2):
     return e, J
 
 
+def stage_depths(d12):
+    """(d1, d2) that every block of the reference's rot-only and tran-only problems gets: init_d[0][0], init_d[1][0]."""
+    d = _f64(d12).reshape(-1, 2)
+    if len(d) < 2:
+        raise ValueError("the reference reads init_d[1][0]: at least two matches")
+    d1, d2 = C.c_double(0), C.c_double(0)
+    lib().orc_stage_depths(_p(d), C.byref(d1), C.byref(d2))
+    return d1.value, d2.value
+
+
+def point_joint(cam1, cam2, rot, tran, d):
+    """Residual e (3,) and Jacobian J (3,8) over [d|rot|tran] of ONE block of the joint problem (dual numbers)."""
+    e, J = np.zeros(3), np.zeros((3, 8))
+    lib().orc_point_joint(_p(_f64(cam1)), _p(_f64(cam2)), _p(_f64(rot)), _p(_f64(tran)), _p(_f64(d)), _p(e), _p(J))
+    return e, J
+
+
+def point_depth(cam1, cam2, rot, tran, d, lam=1.0, c=1.0):
+    """Residuals (5,) and Jacobian (5,2) over d of ONE block of the d-only problem (dual numbers)."""
+    res, J = np.zeros(5), np.zeros((5, 2))
+    lib().orc_point_depth(_p(_f64(cam1)), _p(_f64(cam2)), _p(_f64(rot)), _p(_f64(tran)), C.c_double(lam), C.c_double(c),
+                          _p(_f64(d)), _p(res), _p(J))
+    return res, J
+
+
 def huber(a: float, s: float) -> np.ndarray:
     rho = np.zeros(3)
     lib().orc_huber(C.c_double(a), C.c_double(s), _p(rho))

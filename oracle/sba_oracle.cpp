@@ -8,7 +8,10 @@
 // the rotation, the robust loss and the whole minimiser to Ceres Solver (find_package(Ceres) with
 // no version pin, CMakeLists.txt:12) and ships no test, golden vector or data file that touches the
 // BA path (test/feature_test.cpp exercises the matchers only).  Neither Ceres nor OpenCV exist in
-// this image, so the reference cannot be built or run here.  What follows restates
+// this image, so the reference as a whole cannot be built or run here.  Its cost functors and maps can:
+// oracle/ref_build compiles those files unchanged against stand-in headers, and tests/test_reference_pin_cpu.py
+// holds the per-block functions and the maps below against them byte for byte.  The Ceres boundary itself
+// (AngleAxisRotatePoint, Jet arithmetic, loss, minimiser) stays restated on both sides.  What follows restates
 //   - the reference's own functor bodies, line by line in meaning (citations on each function), and
 //   - Ceres' documented public semantics for AngleAxisRotatePoint, AutoDiffCostFunction (forward-mode
 //     dual numbers), HuberLoss + Corrector, and the default Levenberg-Marquardt trust-region loop.
@@ -44,11 +47,14 @@ template <int N> Dual<N> operator+(const Dual<N>& a, const Dual<N>& b) { Dual<N>
 template <int N> Dual<N> operator-(const Dual<N>& a, const Dual<N>& b) { Dual<N> r; r.v = a.v - b.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] - b.d[i]; return r; }
 template <int N> Dual<N> operator*(const Dual<N>& a, const Dual<N>& b) { Dual<N> r; r.v = a.v * b.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * b.v + a.v * b.d[i]; return r; }
 template <int N> Dual<N> operator/(const Dual<N>& a, const Dual<N>& b) { Dual<N> r; const double inv = 1.0 / b.v; r.v = a.v * inv; for (int i = 0; i < N; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) * inv; return r; }
-template <int N> Dual<N> operator*(double a, const Dual<N>& b) { return Dual<N>(a) * b; }
-template <int N> Dual<N> operator*(const Dual<N>& a, double b) { return a * Dual<N>(b); }
-template <int N> Dual<N> operator-(const Dual<N>& a, double b) { return a - Dual<N>(b); }
-template <int N> Dual<N> operator-(double a, const Dual<N>& b) { return Dual<N>(a) - b; }
-template <int N> Dual<N> operator+(const Dual<N>& a, double b) { return a + Dual<N>(b); }
+// A scalar operand scales (or shifts) both parts, as Ceres documents for Jet; it does not go through the dual product, whose
+// 0 * b.v + a * b.d[i] turns a derivative of -0 into +0.  The values are the same either way; the reference's compiled functors
+// (tests/golden/reference_blocks.npz) showed the sign of those zeros, which this form reproduces.
+template <int N> Dual<N> operator*(double a, const Dual<N>& b) { Dual<N> r; r.v = a * b.v; for (int i = 0; i < N; ++i) r.d[i] = a * b.d[i]; return r; }
+template <int N> Dual<N> operator*(const Dual<N>& a, double b) { Dual<N> r; r.v = a.v * b; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * b; return r; }
+template <int N> Dual<N> operator-(const Dual<N>& a, double b) { Dual<N> r = a; r.v = a.v - b; return r; }
+template <int N> Dual<N> operator-(double a, const Dual<N>& b) { Dual<N> r; r.v = a - b.v; for (int i = 0; i < N; ++i) r.d[i] = -b.d[i]; return r; }
+template <int N> Dual<N> operator+(const Dual<N>& a, double b) { Dual<N> r = a; r.v = a.v + b; return r; }
 template <int N> bool operator>(const Dual<N>& a, double b) { return a.v > b; }
 template <int N> Dual<N> sqrt(const Dual<N>& a) { Dual<N> r; r.v = std::sqrt(a.v); const double k = 0.5 / r.v; for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * k; return r; }
 template <int N> Dual<N> sin(const Dual<N>& a) { Dual<N> r; r.v = std::sin(a.v); const double c = std::cos(a.v); for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * c; return r; }
@@ -395,6 +401,13 @@ void orc_point(int mode, const double* cam1, const double* cam2, const double* r
   point_residual_jacobian(mode, cam1, cam2, rot, tran, d1, d2, e, J);
 }
 
+// The two depths that EVERY block of the rot-only and tran-only problems gets: init_d[0][0] and init_d[1][0] -- the first
+// depth of match 0 and the first depth of match 1, not the pair of one match (.cpp:941-942, :998-999).  d12: n x 2, n >= 2.
+void orc_stage_depths(const double* d12, double* d1, double* d2) {
+  *d1 = d12[2 * 0 + 0];
+  *d2 = d12[2 * 1 + 0];
+}
+
 void orc_huber(double a, double s, double* rho) { huber_evaluate(a, s, rho); }
 
 void orc_rotate(const double* w, const double* p, double* out) { angle_axis_rotate<double>(w, p, out); }
@@ -555,11 +568,34 @@ void depth_residuals(const double cam1[3], const double cam2[3], const double ro
   T r[3] = {T(rot[0]), T(rot[1]), T(rot[2])};
   T t[3] = {T(tran[0]), T(tran[1]), T(tran[2])};
   reprojection_residual(cam1, cam2, d, r, t, res);          // .cpp:1008-1027
-  res[3] = lambda * exp(T(-c) * d[0]);                        // .cpp:1028
-  res[4] = lambda * exp(T(-c) * d[1]);                        // .cpp:1029
+  res[3] = lambda * exp(-c * d[0]);                           // .cpp:1028
+  res[4] = lambda * exp(-c * d[1]);                           // .cpp:1029
 }
 }  // namespace
 extern "C" {
+
+// One residual block of the joint problem as AutoDiffCostFunction<ba_spherical_costfunctor, 3, 2, 3, 3> differentiates it
+// (.cpp:880-887): e[3], J[3][8] row-major over [d (2) | rot (3) | tran (3)], the order of the blocks in AddResidualBlock.
+void orc_point_joint(const double* cam1, const double* cam2, const double* rot, const double* tran, const double* d,
+                     double* e, double* J) {
+  typedef Dual<8> T;
+  T dd[2] = {T::var(d[0], 0), T::var(d[1], 1)};
+  T r[3] = {T::var(rot[0], 2), T::var(rot[1], 3), T::var(rot[2], 4)};
+  T t[3] = {T::var(tran[0], 5), T::var(tran[1], 6), T::var(tran[2], 7)};
+  T res[3];
+  reprojection_residual(cam1, cam2, dd, r, t, res);
+  for (int i = 0; i < 3; ++i) { e[i] = res[i].v; for (int k = 0; k < 8; ++k) J[8 * i + k] = res[i].d[k]; }
+}
+
+// One residual block of the d-only problem, AutoDiffCostFunction<ba_spherical_costfunctor_d_only, 5, 2> (.cpp:1044-1059):
+// res[5] (the three reprojection residuals, lambda exp(-c d0), lambda exp(-c d1)) and J[5][2] row-major.
+void orc_point_depth(const double* cam1, const double* cam2, const double* rot, const double* tran, double lambda, double c,
+                     const double* d, double* res5, double* J) {
+  typedef Dual<2> T;
+  T dd[2] = {T::var(d[0], 0), T::var(d[1], 1)}, res[5];
+  depth_residuals(cam1, cam2, rot, tran, lambda, c, dd, res);
+  for (int i = 0; i < 5; ++i) { res5[i] = res[i].v; J[2 * i] = res[i].d[0]; J[2 * i + 1] = res[i].d[1]; }
+}
 
 int orc_depth_solve(const double* x1, const double* x2, size_t n, const double* rot, const double* tran,
                     double lambda, double c, double* d12 /* in: initial, out: result */, const LmOptions* opt,

@@ -177,6 +177,13 @@ def schur_longdouble(x1, x2, rot, tran, d, radius, delta=1.0, jacobi_scaling=Tru
     columns Jacobi-scaled at this point and damped by clamp(diag) / radius), cost, sum_w."""
     P = JointProblem(x1, x2, delta)
     e, w, E, F = P.blocks(rot, tran, d, dt)
+    return schur_of_blocks(e, w, E, F, radius, delta, jacobi_scaling, min_diag, max_diag, dt)
+
+
+def schur_of_blocks(e, w, E, F, radius, delta=1.0, jacobi_scaling=True, min_diag=1e-6, max_diag=1e32, dt=np.longdouble):
+    """schur_longdouble from given per-match blocks: residuals e (n, 3), weights w (n,), depth columns E (n, 3, 2) and camera
+    columns F (n, 3, 6)."""
+    e, E, F = e.astype(dt), E.astype(dt), F.astype(dt)
     w = w.astype(dt)
     EtE = np.einsum("nri,nrj->nij", E, E) * w[:, None, None]
     EtF = np.einsum("nri,nrj->nij", E, F) * w[:, None, None]

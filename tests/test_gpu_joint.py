@@ -63,10 +63,11 @@ def test_eval_joint_unreduced_block_is_the_rt_sweep(oracle, n, store):
         assert got.n_outlier == n - r.n_inlier
 
 
-def _check_reduced(p, c, x1, x2, radius, what):
+def _check_reduced(p, c, x1, x2, radius, what, schur=rj.schur_longdouble):
+    """schur: what forms the reference system; tests/test_gpu_reference_pin.py forms it from the reference's own blocks."""
     got = p.eval_joint(c.rot_init, c.tran_init, radius)
-    ref = rj.schur_longdouble(x1, x2, c.rot_init, c.tran_init, c.d12, radius)
-    f64 = rj.schur_longdouble(x1, x2, c.rot_init, c.tran_init, c.d12, radius, dt=np.float64)
+    ref = schur(x1, x2, c.rot_init, c.tran_init, c.d12, radius)
+    f64 = schur(x1, x2, c.rot_init, c.tran_init, c.d12, radius, dt=np.float64)
     scale = float(np.abs(ref["V"]).max())
     err_S = float(np.abs(got.S - ref["S"]).max()) / scale
     err_g = float(np.abs(got.gs - ref["gs"]).max()) / max(scale, float(np.abs(ref["gc"]).max()))
