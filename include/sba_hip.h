@@ -24,7 +24,8 @@
  *          sba_problem_solve_resection_weighted(), sba_problem_resection_covariance()
  *   - (no counterpart in the reference) the landmarks kept across frames and improved by each registered frame's bearings
  *       -> sba_landmarks_*()               (a handle of its own; sba_landmarks_fuse: one Kalman update per landmark;
- *                                           sba_landmarks_scores / _prune / _append / _gather: the map edited on the device)
+ *                                           sba_landmarks_scores / _prune / _append / _gather: the map edited on the device;
+ *                                           sba_landmarks_register: a frame's pose and its landmarks solved jointly)
  *   - pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298)
  *       -> sba_keypoints_to_sphere()
  *   - equi2cube::get_all (equi2cube.cpp:12-302)
@@ -694,6 +695,63 @@ int sba_landmarks_append_device(sba_landmarks* h, const void* xyz_dev, const voi
 int sba_landmarks_gather(sba_landmarks* h, const int64_t* idx /* [m] */, size_t m, double* xyz /* double[3 m] or NULL */,
                          double* cov /* double[6 m] or NULL */, uint32_t* counts /* [m] or NULL */);
 int sba_landmarks_gather_device(sba_landmarks* h, const int64_t* idx /* [m], host */, size_t m, void* xyz_dev, void* cov_dev);
+
+/* ---- the landmark map: a frame's pose and its landmarks solved jointly ------------------------------------------------ */
+/* sba_landmarks_register replaces the chain gather -> upload -> weighted resection -> its covariance -> sba_landmarks_fuse by one
+ * call on the map, and removes that chain's two approximations: the pose is no longer treated as independent of the bearings
+ * it was estimated from, and the landmarks' correlation through the shared pose enters every posterior.  Unknowns: the pose
+ * (rot, tran) and every observed landmark X_j with the map's row as its prior N(Xb_j, Sigma_j); the bearing y_j (any length
+ * > 0) is measured with isotropic noise s_j^2 = bearing_sigma^2 d*_j^2 (y_j . y_j) across the ray, FROZEN at the start pose and
+ * Xb_j.  There is no pose prior: the landmarks fix gauge and scale.  With the pose held every landmark is eliminated exactly, so
+ * an evaluation is one streaming pass over the map (csrc/sba_landmarks_register.hpp):
+ *     S = R Sigma R^T + s_j^2 I,  W as in sba_landmarks_fuse,  u = W r,  chi2 = u . u,  T = Sigma R^T W^T,  Xh = Xb + T u
+ *     J_w = W [A(Xh) | I],   H = sum J_w^T J_w,   g = sum J_w^T u,   cost = 1/2 sum chi2
+ * and at the solution, with the pose covariance Sigma_c = H^-1:  X+ = Xh,  Sigma+ = Sigma - T T^T + T J_w Sigma_c J_w^T T^T.
+ * Every observation falls into one class: SKIPPED (a non-finite entry of X or Sigma, a zero or non-finite bearing, a non-finite
+ * d*, S not positive definite across the bearing at the freeze or at the solution, a non-finite result; chi2 = NaN), BEHIND
+ * (d* <= 0 at the freeze or at the solution), GATED (chi2 > chi2_gate AT THE SOLUTION), FUSED.  Observations skipped or behind at
+ * the freeze take no part in the solve.  GATED observations DID take part in it, and so did those found behind only at the
+ * solution: the solve has no robust loss, and a caller who wants them out registers again without them (chi2_out and a dry run
+ * tell which).  Only a fused landmark is rewritten, and its count incremented.
+ * Refusals, all before the first device call with nothing written and the handle usable: a NULL argument, a bad bearing_sigma,
+ * chi2_gate, idx or m: SBA_ERR_INVALID_ARG; lm.huber_delta != 0: SBA_ERR_UNSUPPORTED; a non-finite pose: SBA_ERR_NUMERIC; a
+ * poisoned handle: SBA_ERR_HIP.  After the freeze, with the map untouched: fewer than 3 observations that take part, a failed
+ * solve or an H that is not positive definite at the solution: SBA_ERR_NUMERIC.  An empty map or m == 0: SBA_OK, zero counts
+ * and the start pose.                                                                                                     */
+typedef struct sba_landmark_register_options {
+  double bearing_sigma;        /* radians; finite and >= 0 */
+  double chi2_gate;            /* > 0; +inf: no gate; NaN or <= 0 is refused */
+  int apply;                   /* 0: a dry run -- the pose, its covariance, chi2 and counts, nothing stored */
+  sba_lm_options lm;           /* huber_delta must be 0.  max_num_iterations = 0: register at the given pose -- the freeze, one
+                                  evaluation, the covariance, the write-back */
+} sba_landmark_register_options;
+typedef struct sba_landmark_register_result {
+  double rot[3], tran[3];      /* the solved pose */
+  double cov[36];              /* Sigma_c, row-major over [rot | tran]: the layout of sba_resection_cov.cov */
+  sba_lm_summary summary;
+  long long n_obs;             /* = n_skipped + n_behind + n_gated + n_fused */
+  long long n_skipped, n_behind, n_gated, n_fused;
+  long long n_used;            /* observations that entered the sums at the solution */
+} sba_landmark_register_result;
+typedef struct sba_landmark_register_eval {
+  double H[36];                /* row-major symmetric 6 x 6 over [rot | tran] */
+  double g[6];
+  double cost;
+  long long n_used;            /* observations that entered the sums */
+  long long n_behind;          /* of which: d* <= 0 at the evaluation pose */
+} sba_landmark_register_eval;
+/* One evaluation at (rot, tran) with the noise frozen at (rot_ref, tran_ref); the map is not written.  opt->apply and
+ * opt->chi2_gate (checked all the same) play no part. */
+int sba_landmarks_eval_register(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */,
+                                size_t m, const double rot[3], const double tran[3], const double rot_ref[3],
+                                const double tran_ref[3], const sba_landmark_register_options* opt,
+                                sba_landmark_register_eval* eval);
+/* The solve from (rot0, tran0) and, with opt->apply, the write-back.  idx, bearings and m as for sba_landmarks_fuse (idx ==
+ * NULL: the dense form, m == n, a zero bearing means "not seen").  chi2_out (m doubles, may be NULL) receives every
+ * observation's chi2 at the solution, NaN where skipped.                                                                */
+int sba_landmarks_register(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */, size_t m,
+                           const double rot0[3], const double tran0[3], const sba_landmark_register_options* opt,
+                           sba_landmark_register_result* res, double* chi2_out /* [m] or NULL */);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

@@ -130,6 +130,21 @@ class LmSummary(C.Structure):
                 ("num_line_search_steps", C.c_int)]
 
 
+class LandmarkRegisterOptions(C.Structure):
+    _fields_ = [("bearing_sigma", C.c_double), ("chi2_gate", C.c_double), ("apply", C.c_int), ("lm", LmOptions)]
+
+
+class LandmarkRegisterResult(C.Structure):
+    _fields_ = [("rot", C.c_double * 3), ("tran", C.c_double * 3), ("cov", C.c_double * 36), ("summary", LmSummary),
+                ("n_obs", C.c_longlong), ("n_skipped", C.c_longlong), ("n_behind", C.c_longlong), ("n_gated", C.c_longlong),
+                ("n_fused", C.c_longlong), ("n_used", C.c_longlong)]
+
+
+class LandmarkRegisterEval(C.Structure):
+    _fields_ = [("H", C.c_double * 36), ("g", C.c_double * 6), ("cost", C.c_double), ("n_used", C.c_longlong),
+                ("n_behind", C.c_longlong)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
@@ -214,6 +229,10 @@ SIGNATURES = {
     "sba_landmarks_append_device": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_double]),
     "sba_landmarks_gather": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_size_t, _dp, _dp, C.POINTER(C.c_uint32)]),
     "sba_landmarks_gather_device": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_size_t, _vp, _vp]),
+    "sba_landmarks_eval_register": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp, _dp, _dp,
+                                              C.POINTER(LandmarkRegisterOptions), C.POINTER(LandmarkRegisterEval)]),
+    "sba_landmarks_register": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp, C.POINTER(LandmarkRegisterOptions),
+                                         C.POINTER(LandmarkRegisterResult), _dp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

@@ -117,6 +117,34 @@ class LandmarkFusion:
 
 
 @dataclass
+class LandmarkRegisterEquations:
+    """One evaluation of the joint registration (Landmarks.eval_register): the six-parameter problem over [rot | tran] that is
+    left when every observed landmark has been eliminated exactly at the pose."""
+    H: np.ndarray          # (6, 6) sum J_w^T J_w, the Schur complement of the full Gauss-Newton matrix
+    g: np.ndarray          # (6,)   sum J_w^T u, the exact gradient of the reduced cost
+    cost: float            # 1/2 sum chi2
+    n_used: int            # observations that entered the sums
+    n_behind: int          # of which: the eliminated depth is <= 0 at the evaluation pose
+
+
+@dataclass
+class LandmarkRegistration:
+    """What one Landmarks.register did: the frame's pose and its covariance from the joint solve, and the class of every
+    observation as in LandmarkFusion (gated: chi2 at the SOLUTION > chi2_gate; such observations did take part in the solve)."""
+    rot: np.ndarray        # (3,)
+    tran: np.ndarray       # (3,)
+    cov: np.ndarray        # (6, 6) over [rot | tran]
+    summary: "SolveSummary"
+    n_obs: int
+    n_skipped: int
+    n_behind: int
+    n_gated: int
+    n_fused: int
+    n_used: int            # observations that entered the sums at the solution
+    chi2: np.ndarray | None    # (m,) per observation at the solution, NaN where skipped, or None when not asked for
+
+
+@dataclass
 class LandmarkPrune:
     """What one Landmarks.prune did: every landmark falls into exactly one class, tested in this order, n_before = n_invalid +
     n_uncertain + n_unobserved + n_masked + n_kept.  invalid: a non-finite entry of X or Sigma or a negative variance; uncertain:
@@ -1073,6 +1101,50 @@ class Landmarks:
         cabi.check(self._lib, self._lib.sba_landmarks_fuse(self._h, ip, _dptr(y), m, _dptr(rot), _dptr(tran), C.byref(opt), C.byref(res),
                                                            None if chi2 is None else _dptr(chi2)))
         return LandmarkFusion(int(res.n_obs), int(res.n_skipped), int(res.n_behind), int(res.n_gated), int(res.n_fused), chi2)
+
+    def _register_args(self, bearings, idx, bearing_sigma, chi2_gate, apply, options):
+        y = _f64(bearings).reshape(-1, 3)
+        m = y.shape[0]
+        ii = None
+        if idx is not None:
+            ii = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+            if ii.shape[0] != m:
+                raise ValueError("one index per bearing")
+        opt = cabi.LandmarkRegisterOptions()
+        opt.bearing_sigma, opt.chi2_gate, opt.apply = float(bearing_sigma), float(chi2_gate), 1 if apply else 0
+        opt.lm = options if options is not None else default_lm_options(huber_delta=0.0)
+        return y, m, ii, opt
+
+    def eval_register(self, bearings, rot, tran, rot_ref=None, tran_ref=None, bearing_sigma: float = 0.0,
+                      idx=None) -> LandmarkRegisterEquations:
+        """One evaluation of the joint registration at (rot, tran) with the bearing noise frozen at (rot_ref, tran_ref), by
+        default the same pose.  bearings and idx as for `fuse`.  The map is not written."""
+        y, m, ii, opt = self._register_args(bearings, idx, bearing_sigma, float("inf"), False, None)
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        rot_ref = rot if rot_ref is None else _f64(rot_ref, (3,))
+        tran_ref = tran if tran_ref is None else _f64(tran_ref, (3,))
+        ev = cabi.LandmarkRegisterEval()
+        cabi.check(self._lib, self._lib.sba_landmarks_eval_register(
+            self._h, None if ii is None else ii.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(y), m, _dptr(rot), _dptr(tran), _dptr(rot_ref),
+            _dptr(tran_ref), C.byref(opt), C.byref(ev)))
+        return LandmarkRegisterEquations(np.array(ev.H, dtype=np.float64).reshape(6, 6), np.array(ev.g, dtype=np.float64), float(ev.cost),
+                                         int(ev.n_used), int(ev.n_behind))
+
+    def register(self, bearings, rot, tran, bearing_sigma: float = 0.0, chi2_gate: float = float("inf"), idx=None, apply: bool = True,
+                 options: cabi.LmOptions | None = None, return_chi2: bool = False) -> LandmarkRegistration:
+        """Solve the frame's pose and every observed landmark jointly from the start (rot, tran), and with `apply` write the
+        landmarks' posteriors back.  bearings and idx as for `fuse`.  options: LM options with huber_delta = 0 (the default here);
+        max_num_iterations = 0 registers at the given pose.  apply False: a dry run."""
+        y, m, ii, opt = self._register_args(bearings, idx, bearing_sigma, chi2_gate, apply, options)
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        chi2 = np.full(m, np.nan) if return_chi2 else None
+        res = cabi.LandmarkRegisterResult()
+        cabi.check(self._lib, self._lib.sba_landmarks_register(
+            self._h, None if ii is None else ii.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(y), m, _dptr(rot), _dptr(tran), C.byref(opt),
+            C.byref(res), None if chi2 is None else _dptr(chi2)))
+        return LandmarkRegistration(np.array(res.rot, dtype=np.float64), np.array(res.tran, dtype=np.float64),
+                                    np.array(res.cov, dtype=np.float64).reshape(6, 6), _summary(res.summary), int(res.n_obs),
+                                    int(res.n_skipped), int(res.n_behind), int(res.n_gated), int(res.n_fused), int(res.n_used), chi2)
 
     # -- edits: the counts survive all of them -------------------------------------------------------
     def scores(self) -> np.ndarray:

@@ -502,6 +502,22 @@ hipError_t launch_landmarks_unpack(const LandmarkPlanes& pl, size_t n, double* x
 hipError_t launch_landmarks_fuse(const LandmarkPlanes& pl, const LandmarkFuseParams& prm, const long long* idx, const double* bearings,
                                  double* chi2, unsigned long long* counters, bool apply, int grid, hipStream_t stream);
 
+// The joint registration of a frame against the landmark map (sba_landmarks_register.hip; the per-observation code and
+// LandmarkRegisterParams, a by-value kernel argument: sba_landmarks_register.hpp).  idx null = dense (bearings [elems][3], zeros
+// beyond n; noise and chi2 [elems]), else m observations.  Freeze: the noise plane and the freeze's class counts (slot
+// LANDMARK_FUSED: the observations that take part) in `counters` (4 words, zeroed by the launcher).  Reduce: partials
+// [grid][JOINT_ROW], grid >= 1, the SBA_RESECT_* slots in out (device).  Apply: the write-back (apply) or the dry run, chi2 may be
+// null, the four class counts in `counters` (zeroed by the launcher).
+struct LandmarkRegisterParams;
+enum { LANDMARK_REGISTER_FREEZE = 0, LANDMARK_REGISTER_REDUCE = 1, LANDMARK_REGISTER_APPLY = 2, LANDMARK_REGISTER_KERNELS = 3 };
+hipError_t landmarks_register_blocks_per_cu(int which, bool indexed, bool apply, int* blocks);   // resident 256-thread blocks per CU
+hipError_t launch_landmarks_register_freeze(const LandmarkPlanes& pl, const LandmarkRegisterParams& prm, const long long* idx, const double* bearings,
+                                            double* noise, unsigned long long* counters, int grid, hipStream_t stream);
+hipError_t launch_landmarks_register_reduce(const LandmarkPlanes& pl, const LandmarkRegisterParams& prm, const long long* idx, const double* bearings,
+                                            const double* noise, double* partials, int grid, double* out, hipStream_t stream);
+hipError_t launch_landmarks_register_apply(const LandmarkPlanes& pl, const LandmarkRegisterParams& prm, const long long* idx, const double* bearings,
+                                           const double* noise, double* chi2, unsigned long long* counters, bool apply, int grid, hipStream_t stream);
+
 // Edits of the landmark map (sba_landmarks_edit.hip; the score, the classes of a prune and the checks: sba_landmarks_edit.hpp).
 // Scores: out [elems] doubles (device, 16-byte aligned).  Keep: one streaming pass that writes keep[ntiles * kCompactTile] bytes
 // (1 = kept, 0 beyond n) and adds the LANDMARK_PRUNE_CLASSES class counts to `counters` (zeroed by the launcher):

@@ -2,18 +2,23 @@
 // 3 x 3 covariances and observation counts on the device as planes, and fuses a registered frame's bearings into them, one
 // streaming pass per frame.  Kernels: sba_landmarks.hip; the per-observation code, the state of a pass and the option and
 // index checks: sba_landmarks.hpp.  Below them the edits of the map -- scores, prune, append, gather -- with their kernels in
-// sba_landmarks_edit.hip and their checks in sba_landmarks_edit.hpp.  Every wait is the bounded stream_wait; a handle whose wait
-// gave up is poisoned.
+// sba_landmarks_edit.hip and their checks in sba_landmarks_edit.hpp, and at the end the joint registration of a frame -- its pose
+// and its landmarks solved together -- with its kernels in sba_landmarks_register.hip and its per-observation code in
+// sba_landmarks_register.hpp.  Every wait is the bounded stream_wait; a handle whose wait gave up is poisoned.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "sba_internal.hpp"
 #include "sba_landmarks.hpp"
 #include "sba_landmarks_edit.hpp"
+#include "sba_landmarks_register.hpp"
+#include "sba_lm.hpp"
 
 struct sba_landmarks {
   int device = 0;
@@ -37,6 +42,11 @@ struct sba_landmarks {
   void* edit = nullptr;
   size_t edit_bytes = 0;
   int occ_edit[sba::LANDMARK_EDIT_KERNELS] = {0, 0, 0, 0};
+  // The joint registration (at the end of this file): the freeze's 4 class counters, the reduce pass's folded row and its block
+  // rows [grid][JOINT_ROW], kept across calls.  The noise plane lives behind idx in the observation scratch.
+  void* reg = nullptr;
+  size_t reg_bytes = 0;
+  int occ_reg[sba::LANDMARK_REGISTER_KERNELS][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};   // per [kernel][indexed][apply]
 };
 
 namespace {
@@ -175,6 +185,7 @@ int sba_landmarks_destroy(sba_landmarks* h) {
   if (h->obs) (void)hipFree(h->obs);
   if (h->planes_alt) (void)hipFree(h->planes_alt);
   if (h->edit) (void)hipFree(h->edit);
+  if (h->reg) (void)hipFree(h->reg);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return SBA_OK;
@@ -479,6 +490,222 @@ int sba_landmarks_gather(sba_landmarks* h, const int64_t* idx, size_t m, double*
 
 int sba_landmarks_gather_device(sba_landmarks* h, const int64_t* idx, size_t m, void* xyz_dev, void* cov_dev) {
   return gather_common(h, idx, m, xyz_dev, cov_dev, nullptr, true);
+}
+
+}  // extern "C"
+
+// ---- the joint registration: a frame's pose and its landmarks solved together ----------------------------------------------------
+namespace {
+
+// What one registration works on, after the refusals: the observations on the device, the frozen noise, the block rows.
+struct RegisterWork {
+  bool indexed = false;
+  size_t m = 0;
+  double bearing_sigma = 0.0;
+  unsigned long long* counters = nullptr;      // the apply pass's class counts (observation scratch)
+  double *chi2_dev = nullptr, *bearings_dev = nullptr, *noise_dev = nullptr;
+  long long* idx_dev = nullptr;
+  unsigned long long* freeze_counters = nullptr;
+  double *row_dev = nullptr, *partials = nullptr;
+  int grid_freeze = 0, grid_reduce = 0;
+  long long freeze_counts[sba::LANDMARK_CLASSES] = {0, 0, 0, 0};
+};
+
+int register_occ(sba_landmarks* h, int which, bool indexed, bool apply, int* occ) {
+  int& o = h->occ_reg[which][indexed ? 1 : 0][apply ? 1 : 0];
+  if (o == 0) {
+    SBA_TRY_HIP(sba::landmarks_register_blocks_per_cu(which, indexed, apply, &o));
+    o = std::max(1, o);
+  }
+  *occ = o;
+  return SBA_OK;
+}
+
+// The refusals sba_landmarks_eval_register and sba_landmarks_register share, all before the first device call.
+int register_check(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double* rot, const double* tran,
+                   const double* rot_ref, const double* tran_ref, const sba_landmark_register_options* opt, const void* out) {
+  if (!h || !rot || !tran || !rot_ref || !tran_ref || !opt || !out || (m > 0 && !bearings)) return sba::set_error(SBA_ERR_INVALID_ARG, "null argument");
+  SBA_REFUSE_POISONED(h);
+  if (const char* why = sba::resect_weight_check_sigma(opt->bearing_sigma)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
+  if (const char* why = sba::landmark_check_gate(opt->chi2_gate)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
+  if (const char* why = sba::landmark_check_index(idx, m, h->n)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (m = %zu, n = %zu)", why, m, h->n);
+  if (const char* why = sba::landmark_register_check_loss(opt->lm.huber_delta)) return sba::set_error(SBA_ERR_UNSUPPORTED, "%s", why);
+  if (!finite3(rot) || !finite3(tran) || !finite3(rot_ref) || !finite3(tran_ref)) return sba::set_error(SBA_ERR_NUMERIC, "non-finite rot/tran");
+  return SBA_OK;
+}
+
+// Upload bearings and idx as sba_landmarks_fuse does, size the scratch, freeze the noise at (rot_ref, tran_ref) and fetch the
+// freeze's class counts.
+int register_freeze(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double rot_ref[3], const double tran_ref[3],
+                    double bearing_sigma, RegisterWork* w) {
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  // counters | chi2 [elems] | bearings [elems][3] | idx [elems] | noise [elems]: sba_landmarks_fuse's layout, then the noise plane
+  const size_t elems = h->elems, need = 32 + elems * 6 * sizeof(double);
+  if (h->obs_bytes < need) {
+    if (h->obs) SBA_TRY_HIP(hipFree(h->obs));
+    h->obs = nullptr; h->obs_bytes = 0;
+    SBA_TRY_HIP(hipMalloc(&h->obs, need));
+    h->obs_bytes = need;
+  }
+  w->indexed = idx != nullptr;
+  w->m = m;
+  w->bearing_sigma = bearing_sigma;
+  w->counters = static_cast<unsigned long long*>(h->obs);
+  w->chi2_dev = reinterpret_cast<double*>(w->counters + 4);
+  w->bearings_dev = w->chi2_dev + elems;
+  w->idx_dev = reinterpret_cast<long long*>(w->bearings_dev + 3 * elems);
+  w->noise_dev = reinterpret_cast<double*>(w->idx_dev + elems);
+  static_assert(sba::LANDMARK_CLASSES == 4 && sizeof(long long) == sizeof(int64_t), "layout of the observation scratch");
+  const size_t items = w->indexed ? m : elems / 2;
+  int occ = 1;
+  int rc = register_occ(h, sba::LANDMARK_REGISTER_FREEZE, w->indexed, false, &occ);
+  if (rc) return rc;
+  w->grid_freeze = grid_for(h, items, occ);
+  // The reduce pass: two observations per lane in both forms and one grid rule for both (the smaller occupancy), so that the
+  // indexed form over every landmark folds the dense form's block rows.
+  int occ_other = 1;
+  rc = register_occ(h, sba::LANDMARK_REGISTER_REDUCE, w->indexed, false, &occ);
+  if (rc) return rc;
+  rc = register_occ(h, sba::LANDMARK_REGISTER_REDUCE, !w->indexed, false, &occ_other);
+  if (rc) return rc;
+  w->grid_reduce = grid_for(h, w->indexed ? (m + 1) / 2 : elems / 2, std::min(occ, occ_other));
+  // freeze counters (32 B) | the folded row | block rows [grid]
+  const size_t reg_need = 32 + (static_cast<size_t>(w->grid_reduce) + 1) * sba::JOINT_ROW * sizeof(double);
+  if (h->reg_bytes < reg_need) {
+    if (h->reg) SBA_TRY_HIP(hipFree(h->reg));
+    h->reg = nullptr; h->reg_bytes = 0;
+    SBA_TRY_HIP(hipMalloc(&h->reg, reg_need));
+    h->reg_bytes = reg_need;
+  }
+  w->freeze_counters = static_cast<unsigned long long*>(h->reg);
+  w->row_dev = reinterpret_cast<double*>(w->freeze_counters + 4);
+  w->partials = w->row_dev + sba::JOINT_ROW;
+  SBA_TRY_HIP(hipMemcpyAsync(w->bearings_dev, bearings, 3 * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (idx) SBA_TRY_HIP(hipMemcpyAsync(w->idx_dev, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  else if (elems > m) SBA_TRY_HIP(hipMemsetAsync(w->bearings_dev + 3 * m, 0, 3 * (elems - m) * sizeof(double), h->stream));   // the padding row: not seen
+  sba::LandmarkRegisterParams prm;
+  sba::landmark_register_fill(h->n, m, rot_ref, tran_ref, nullptr, bearing_sigma, INFINITY, &prm);
+  SBA_TRY_HIP(sba::launch_landmarks_register_freeze(planes_of(h), prm, w->indexed ? w->idx_dev : nullptr, w->bearings_dev, w->noise_dev,
+                                                    w->freeze_counters, w->grid_freeze, h->stream));
+  unsigned long long host_counts[4] = {0, 0, 0, 0};
+  SBA_TRY_HIP(hipMemcpyAsync(host_counts, w->freeze_counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "landmark registration freeze", &h->poisoned);
+  if (rc) return rc;
+  for (int k = 0; k < sba::LANDMARK_CLASSES; ++k) w->freeze_counts[k] = static_cast<long long>(host_counts[k]);
+  return SBA_OK;
+}
+
+// One evaluation at (rot, tran): the reduce pass, the fold, the row fetched through the bounded wait.
+int register_reduce_pass(sba_landmarks* h, const RegisterWork& w, const double rot[3], const double tran[3], double* row) {
+  sba::LandmarkRegisterParams prm;
+  sba::landmark_register_fill(h->n, w.m, rot, tran, nullptr, w.bearing_sigma, INFINITY, &prm);
+  SBA_TRY_HIP(sba::launch_landmarks_register_reduce(planes_of(h), prm, w.indexed ? w.idx_dev : nullptr, w.bearings_dev, w.noise_dev, w.partials,
+                                                    w.grid_reduce, w.row_dev, h->stream));
+  SBA_TRY_HIP(hipMemcpyAsync(row, w.row_dev, SBA_RESECT_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return sba::stream_wait(h->stream, "landmark registration reduce pass", &h->poisoned);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sba_landmarks_eval_register(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double rot[3], const double tran[3],
+                                const double rot_ref[3], const double tran_ref[3], const sba_landmark_register_options* opt,
+                                sba_landmark_register_eval* eval) {
+  int rc = register_check(h, idx, bearings, m, rot, tran, rot_ref, tran_ref, opt, eval);
+  if (rc) return rc;
+  *eval = sba_landmark_register_eval{};
+  if (h->n == 0 || m == 0) return SBA_OK;
+  RegisterWork w;
+  rc = register_freeze(h, idx, bearings, m, rot_ref, tran_ref, opt->bearing_sigma, &w);
+  if (rc) return rc;
+  double row[sba::JOINT_ROW] = {0};
+  rc = register_reduce_pass(h, w, rot, tran, row);
+  if (rc) return rc;
+  if (!sba::resect_row_finite(row)) return sba::set_error(SBA_ERR_NUMERIC, "non-finite registration sums");
+  sba_normal_eq ne;
+  double n_behind = 0.0;
+  sba::resect_expand_row(row, &ne, &n_behind);
+  std::memcpy(eval->H, ne.H, sizeof(ne.H));
+  std::memcpy(eval->g, ne.g, sizeof(ne.g));
+  eval->cost = ne.cost;
+  eval->n_used = static_cast<long long>(ne.sum_w);
+  eval->n_behind = static_cast<long long>(n_behind);
+  return SBA_OK;
+}
+
+int sba_landmarks_register(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double rot0[3], const double tran0[3],
+                           const sba_landmark_register_options* opt, sba_landmark_register_result* res, double* chi2_out) {
+  int rc = register_check(h, idx, bearings, m, rot0, tran0, rot0, tran0, opt, res);
+  if (rc) return rc;
+  *res = sba_landmark_register_result{};
+  for (int a = 0; a < 3; ++a) { res->rot[a] = rot0[a]; res->tran[a] = tran0[a]; }
+  if (h->n == 0 || m == 0) return SBA_OK;
+  const auto t_start = std::chrono::steady_clock::now();
+  RegisterWork w;
+  rc = register_freeze(h, idx, bearings, m, rot0, tran0, opt->bearing_sigma, &w);
+  if (rc) return rc;
+  if (w.freeze_counts[sba::LANDMARK_LIVE] < 3)
+    return sba::set_error(SBA_ERR_NUMERIC, "pose not determined: %lld observations take part after the freeze (%lld skipped, %lld behind), 3 are needed",
+                          w.freeze_counts[sba::LANDMARK_LIVE], w.freeze_counts[sba::LANDMARK_SKIPPED], w.freeze_counts[sba::LANDMARK_BEHIND]);
+  struct Visit { double rot[3], tran[3], H[36], n_used; };
+  std::vector<Visit> visits;
+  double seconds_eval = 0.0;
+  int eval_rc = SBA_OK;
+  auto evaluate = [&](const double r[3], const double t[3], sba_normal_eq* ne) -> bool {
+    const auto t0 = std::chrono::steady_clock::now();
+    double row[sba::JOINT_ROW] = {0};
+    eval_rc = register_reduce_pass(h, w, r, t, row);
+    seconds_eval += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (eval_rc) return false;
+    if (!sba::resect_row_finite(row)) return false;
+    sba::resect_expand_row(row, ne, nullptr);
+    Visit v;
+    for (int a = 0; a < 3; ++a) { v.rot[a] = r[a]; v.tran[a] = t[a]; }
+    std::memcpy(v.H, ne->H, sizeof(v.H));
+    v.n_used = ne->sum_w;
+    visits.push_back(v);
+    return true;
+  };
+  double r[3] = {rot0[0], rot0[1], rot0[2]}, t[3] = {tran0[0], tran0[1], tran0[2]};
+  sba_lm_summary sum;
+  std::memset(&sum, 0, sizeof(sum));
+  const int status = sba::lm_solve(SBA_MODE_RT, r, t, opt->lm, evaluate, &sum);
+  if (eval_rc) return eval_rc;
+  sum.seconds_eval = seconds_eval;
+  if (status != SBA_OK) return sba::set_error(status, "joint registration solve failed: non-finite sums or 5 consecutive invalid steps");
+  const Visit* at = nullptr;
+  for (size_t k = visits.size(); k-- > 0;)
+    if (std::memcmp(visits[k].rot, r, sizeof(r)) == 0 && std::memcmp(visits[k].tran, t, sizeof(t)) == 0) { at = &visits[k]; break; }
+  double cov[36];
+  if (!at || !sba::resect_cov_inverse(at->H, cov))
+    return sba::set_error(SBA_ERR_NUMERIC, "pose not determined: the reduced normal matrix is not positive definite at the solution");
+  // the write-back at the solution
+  const bool apply = opt->apply != 0;
+  int occ = 1;
+  rc = register_occ(h, sba::LANDMARK_REGISTER_APPLY, w.indexed, apply, &occ);
+  if (rc) return rc;
+  sba::LandmarkRegisterParams prm;
+  sba::landmark_register_fill(h->n, m, r, t, cov, opt->bearing_sigma, opt->chi2_gate, &prm);
+  SBA_TRY_HIP(sba::launch_landmarks_register_apply(planes_of(h), prm, w.indexed ? w.idx_dev : nullptr, w.bearings_dev, w.noise_dev,
+                                                   chi2_out ? w.chi2_dev : nullptr, w.counters, apply,
+                                                   grid_for(h, w.indexed ? m : h->elems / 2, occ), h->stream));
+  unsigned long long host_counts[4] = {0, 0, 0, 0};
+  SBA_TRY_HIP(hipMemcpyAsync(host_counts, w.counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
+  if (chi2_out) SBA_TRY_HIP(hipMemcpyAsync(chi2_out, w.chi2_dev, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "landmark registration write-back", &h->poisoned);
+  if (rc) return rc;
+  for (int a = 0; a < 3; ++a) { res->rot[a] = r[a]; res->tran[a] = t[a]; }
+  std::memcpy(res->cov, cov, sizeof(cov));
+  res->n_skipped = static_cast<long long>(host_counts[sba::LANDMARK_SKIPPED]);
+  res->n_behind = static_cast<long long>(host_counts[sba::LANDMARK_BEHIND]);
+  res->n_gated = static_cast<long long>(host_counts[sba::LANDMARK_GATED]);
+  res->n_fused = static_cast<long long>(host_counts[sba::LANDMARK_FUSED]);
+  res->n_obs = res->n_skipped + res->n_behind + res->n_gated + res->n_fused;
+  res->n_used = static_cast<long long>(at->n_used);
+  sum.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+  res->summary = sum;
+  return SBA_OK;
 }
 
 }  // extern "C"

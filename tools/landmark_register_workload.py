@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Workload for tools/profile_landmark_register.sh: the joint registration of a frame against the landmark map at 10^7 landmarks,
+dense, next to the d-only stage's pass and the fusion's dry run as the yardsticks of the same run.
+
+    python tools/landmark_register_workload.py [n] [calls]
+
+In ONE process (one box: boxes differ by ~6 %), on the scene of tools/landmark_fusion_workload.py without its wrong matches (landmarks
+d1 * x1 drawn from a seeded covariance per landmark; bearings x2), the start 2e-3 rad and 1e-2 units off the true pose:
+  * 10 iterations of the d-only stage                               -> depth_step_kernel: the YARDSTICK of the run
+  * one set, `calls` fusion dry runs without a pose covariance      -> landmarks_fuse_kernel<false, false>: the second yardstick
+  * `calls` registrations as dry runs (apply = False)               -> landmarks_register_freeze_kernel<false> once per call,
+                                                                       landmarks_register_reduce_kernel<false> once per evaluation,
+                                                                       landmarks_register_apply_kernel<false, false> once per call
+  * 3 indexed dry-run registrations over every second landmark      -> the <true> instances
+  * `calls` times the SEQUENTIAL CHAIN the registration replaces, through a Problem, as a dry run as well: get_device (the dense
+    frame's gather_device) -> upload_device -> set_landmark_covariances_device -> solve_resection_weighted -> resection_covariance
+    -> fuse.  Its wall time against the registration's is the comparison of the speed table: against the existing route.
+  * one registration with apply = True                              -> landmarks_register_apply_kernel<false, true>
+Every registration and every fusion uploads its 24 n bytes of bearings from the host first, and so does the chain (once, for the
+Problem): the host-side wall times hold those copies, the kernel trace does not.  Prints one JSON line with host-side wall times;
+the kernel times come from the rocprofv3 kernel trace."""
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from landmark_fusion_workload import covariances  # noqa: E402
+from spherical_bundle_adjuster_amd import api, synthetic  # noqa: E402
+
+
+def timed(calls, f):
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        r = f()
+    return 1e3 * (time.perf_counter() - t0) / calls, r
+
+
+def main():
+    import torch
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
+    calls = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    out = {"n": n, "calls": calls}
+    c = synthetic.full_rt(n, seed=synthetic.BASE_SEED + 5, outlier_fraction=0.0)     # no wrong matches: the joint solve has no robust loss
+    rot, tran = c.rot_true, c.tran_true
+    truth = c.x1 * c.d12[:, :1]
+    cov, draw = covariances(truth, synthetic.BASE_SEED + 6)
+    X = truth + draw
+    rng = np.random.default_rng(synthetic.BASE_SEED + 7)
+    unit = lambda v: v / np.linalg.norm(v)
+    rot0, tran0 = rot + 2e-3 * unit(rng.standard_normal(3)), tran + 1e-2 * unit(rng.standard_normal(3))
+    opt = api.default_lm_options(huber_delta=0.0)
+    with api.Problem(0) as p:
+        p.upload(c.x1, c.x2, np.full((n, 2), 5.0))
+        _, sd = p.solve_depths(rot, tran, options=api.default_lm_options(max_num_iterations=10))
+        out["depth_stage_us_per_pass"] = sd.seconds_total / max(sd.num_evaluations, 1) * 1e6
+    dev = torch.device("cuda", 0)
+    with api.Landmarks(0) as L, api.Problem(0) as q:
+        out["set_ms"], _ = timed(1, lambda: L.set(X, cov))
+        L.fuse(c.x2, rot, tran, 1e-3, 9.21, apply=False, want_chi2=False)                    # first call: occupancy query, scratch
+        out["fuse_dry_host_ms"], _ = timed(calls, lambda: L.fuse(c.x2, rot, tran, 1e-3, 9.21, apply=False, want_chi2=False))
+        reg = lambda **kw: L.register(c.x2, rot0, tran0, 1e-3, 9.21, options=opt, **kw)
+        reg(apply=False)                                                                     # first call: occupancy queries, scratch
+        out["register_dry_host_ms"], f = timed(calls, lambda: reg(apply=False))
+        out["register"] = {"termination": f.summary.termination, "iterations": f.summary.num_iterations, "evaluations": f.summary.num_evaluations,
+                           "seconds_eval": f.summary.seconds_eval, "n_fused": f.n_fused, "n_gated": f.n_gated, "n_used": f.n_used,
+                           "pose_error": [float(np.abs(f.rot - rot).max()), float(np.abs(f.tran - tran).max())]}
+        idx = np.arange(0, n, 2, dtype=np.int64)
+        y2 = np.ascontiguousarray(c.x2[idx])
+        out["register_indexed_dry_host_ms"], h = timed(3, lambda: L.register(y2, rot0, tran0, 1e-3, 9.21, idx=idx, apply=False, options=opt))
+        out["indexed"] = {"m": int(len(idx)), "n_fused": h.n_fused, "evaluations": h.summary.num_evaluations}
+        # the sequential chain through a Problem, on the device
+        tx = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        tc = torch.zeros((n, 6), dtype=torch.float64, device=dev)
+        ones = torch.ones((n, 2), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+
+        def chain():
+            L.get_device(tx.data_ptr(), tc.data_ptr())
+            ty = torch.from_numpy(c.x2).to(dev)
+            torch.cuda.synchronize()
+            q.upload_device(tx.data_ptr(), ty.data_ptr(), ones.data_ptr(), n)
+            q.set_landmark_covariances_device(tc.data_ptr(), 1.0)
+            r, t, sm, _ = q.solve_resection_weighted(rot0, tran0, options=opt, bearing_sigma=1e-3, reweight_rounds=1, store_depths=False)
+            cv = q.resection_covariance(r, t, opt)
+            return sm, L.fuse(c.x2, r, t, 1e-3, 9.21, cv.cov, apply=False, want_chi2=False)
+        chain()
+        out["chain_dry_host_ms"], (sm, g) = timed(calls, chain)
+        out["chain"] = {"iterations": sm.num_iterations, "evaluations": sm.num_evaluations, "n_fused": g.n_fused, "n_gated": g.n_gated}
+        out["register_apply_host_ms"], a = timed(1, lambda: reg(apply=True))
+        Xg, Cg = L.get()
+        out["result"] = {"finite": bool(np.isfinite(Xg).all() and np.isfinite(Cg).all()), "max_count": int(L.counts().max()),
+                         "n_fused": a.n_fused, "rms_before": float(np.sqrt(np.mean(np.sum(draw ** 2, axis=1)))),
+                         "rms_after": float(np.sqrt(np.mean(np.sum((Xg - truth) ** 2, axis=1))))}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
