@@ -63,46 +63,128 @@ int grid_for(const sba_landmarks* h, size_t items, int occ) {
   return static_cast<int>(std::min<size_t>({blocks, static_cast<size_t>(h->num_cus) * static_cast<size_t>(std::max(1, occ)), static_cast<size_t>(cap)}));
 }
 
-int pack_occ(sba_landmarks* h, bool unpack, int* occ) {
-  int& o = h->occ_pack[unpack ? 1 : 0];
-  if (o == 0) {
-    SBA_TRY_HIP(sba::landmarks_pack_blocks_per_cu(unpack, &o));
-    o = std::max(1, o);
+// Resident blocks per CU of a kernel, asked once per handle and kernel: *slot is 0 while unknown, at least 1 afterwards.
+template <typename Query>
+int cached_occ(int* slot, Query query, int* occ) {
+  if (*slot == 0) {
+    SBA_TRY_HIP(query(slot));
+    *slot = std::max(1, *slot);
   }
-  *occ = o;
+  *occ = *slot;
+  return SBA_OK;
+}
+int pack_occ(sba_landmarks* h, bool unpack, int* occ) {
+  return cached_occ(&h->occ_pack[unpack ? 1 : 0], [&](int* o) { return sba::landmarks_pack_blocks_per_cu(unpack, o); }, occ);
+}
+int fuse_occ(sba_landmarks* h, bool indexed, bool apply, int* occ) {
+  return cached_occ(&h->occ_fuse[indexed ? 1 : 0][apply ? 1 : 0], [&](int* o) { return sba::landmarks_fuse_blocks_per_cu(indexed, apply, o); }, occ);
+}
+int edit_occ(sba_landmarks* h, int which, int* occ) {
+  return cached_occ(&h->occ_edit[which], [&](int* o) { return sba::landmarks_edit_blocks_per_cu(which, o); }, occ);
+}
+int register_occ(sba_landmarks* h, int which, bool indexed, bool apply, int* occ) {
+  return cached_occ(&h->occ_reg[which][indexed ? 1 : 0][apply ? 1 : 0],
+                    [&](int* o) { return sba::landmarks_register_blocks_per_cu(which, indexed, apply, o); }, occ);
+}
+
+// Grow-only device scratch of a handle: at least `need` bytes behind *ptr afterwards.  What it held is lost when it grows.
+// growth_den = 0: it grows exactly to `need`; d > 0: by 1 / d of its old size at least (an allocation that is outgrown again and
+// again; 2 = by half).
+template <typename T>
+int grow_scratch(T** ptr, size_t* bytes, size_t need, size_t growth_den = 0) {
+  if (*bytes >= need) return SBA_OK;
+  const size_t cap = growth_den ? std::max(need, *bytes + *bytes / growth_den) : need;
+  if (*ptr) SBA_TRY_HIP(hipFree(*ptr));
+  *ptr = nullptr; *bytes = 0;
+  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(ptr), cap));
+  *bytes = cap;
   return SBA_OK;
 }
 
 bool finite3(const double* a) { return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]); }
 
+// Rows on the device are moved in place as 16-byte vectors; rows on the host are staged and may lie anywhere.
+bool rows_unaligned(bool on_device, const void* xyz, const void* cov) {
+  return on_device && ((reinterpret_cast<uintptr_t>(xyz) | reinterpret_cast<uintptr_t>(cov)) & 15u) != 0;
+}
+
+// n caller rows between the host and 9 n doubles of device staging `s`: covariance rows first, 48 n bytes keep the landmark rows
+// 16-byte aligned.  Down: the arrays that are asked for.
+int stage_rows_up(sba_landmarks* h, double* s, const void* xyz, const void* cov, size_t n) {
+  SBA_TRY_HIP(hipMemcpyAsync(s, cov, 6 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  SBA_TRY_HIP(hipMemcpyAsync(s + 6 * n, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  return SBA_OK;
+}
+int stage_rows_down(sba_landmarks* h, const double* s, size_t n, void* xyz, void* cov) {
+  if (cov) SBA_TRY_HIP(hipMemcpyAsync(cov, s, 6 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (xyz) SBA_TRY_HIP(hipMemcpyAsync(xyz, s + 6 * n, 3 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return SBA_OK;
+}
+
+// The observations of one pass on the device (h->obs, kept across calls):
+//   counters (LANDMARK_CLASSES words) | chi2 [elems] | bearings [elems][3] | idx [elems] | noise [elems] (the registration only)
+// Every part starts 16-byte aligned (elems is even).
+struct ObsScratch {
+  unsigned long long* counters = nullptr;
+  double *chi2 = nullptr, *bearings = nullptr;
+  long long* idx = nullptr;
+  double* noise = nullptr;
+};
+constexpr size_t kCounterBytes = sba::LANDMARK_CLASSES * sizeof(unsigned long long);
+static_assert(kCounterBytes % 16 == 0 && sizeof(long long) == sizeof(int64_t), "layout of the observation scratch");
+
+int obs_scratch(sba_landmarks* h, bool with_noise, ObsScratch* s) {
+  const size_t elems = h->elems;
+  const int rc = grow_scratch(&h->obs, &h->obs_bytes, kCounterBytes + elems * (with_noise ? 6 : 5) * sizeof(double));
+  if (rc) return rc;
+  s->counters = static_cast<unsigned long long*>(h->obs);
+  s->chi2 = reinterpret_cast<double*>(s->counters + sba::LANDMARK_CLASSES);
+  s->bearings = s->chi2 + elems;
+  s->idx = reinterpret_cast<long long*>(s->bearings + 3 * elems);
+  s->noise = with_noise ? reinterpret_cast<double*>(s->idx + elems) : nullptr;
+  return SBA_OK;
+}
+
+// m bearings and, in the indexed form, their idx into the scratch.  The dense form's padding row is zeroed: loaded, not seen.
+int upload_observations(sba_landmarks* h, const ObsScratch& s, const int64_t* idx, const double* bearings, size_t m) {
+  SBA_TRY_HIP(hipMemcpyAsync(s.bearings, bearings, 3 * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (idx) SBA_TRY_HIP(hipMemcpyAsync(s.idx, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  else if (h->elems > m) SBA_TRY_HIP(hipMemsetAsync(s.bearings + 3 * m, 0, 3 * (h->elems - m) * sizeof(double), h->stream));
+  return SBA_OK;
+}
+
+// The class counts of a fusion pass or of a registration's write-back into the result's fields.
+template <typename Result>
+void counts_to_result(const unsigned long long* c, Result* res) {
+  res->n_skipped = static_cast<long long>(c[sba::LANDMARK_SKIPPED]);
+  res->n_behind = static_cast<long long>(c[sba::LANDMARK_BEHIND]);
+  res->n_gated = static_cast<long long>(c[sba::LANDMARK_GATED]);
+  res->n_fused = static_cast<long long>(c[sba::LANDMARK_FUSED]);
+  res->n_obs = res->n_skipped + res->n_behind + res->n_gated + res->n_fused;
+}
+
 int set_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n, double cov_scale, bool from_device) {
   if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
   SBA_REFUSE_POISONED(h);
   if (n > 0 && (!xyz || !cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark or covariance array");
-  if (from_device && ((reinterpret_cast<uintptr_t>(xyz) | reinterpret_cast<uintptr_t>(cov)) & 15u))
-    return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
+  if (rows_unaligned(from_device, xyz, cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
   if (const char* why = sba::resect_weight_check_scale(cov_scale)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
   SBA_TRY_HIP(hipSetDevice(h->device));
-  const size_t elems = (n + 1) / 2 * 2, bytes = planes_size(elems);
+  const size_t elems = (n + 1) / 2 * 2;
   h->n = 0; h->elems = 0;        // the map is replaced: empty until the new rows are in place
   if (n == 0) return SBA_OK;
-  if (h->planes_bytes < bytes) {
-    if (h->planes) SBA_TRY_HIP(hipFree(h->planes));
-    h->planes = nullptr; h->planes_bytes = 0;
-    SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&h->planes), bytes));
-    h->planes_bytes = bytes;
-  }
+  int rc = grow_scratch(&h->planes, &h->planes_bytes, planes_size(elems));
+  if (rc) return rc;
   sba::DeviceBuffer staging(&h->poisoned);
   const double *xyz_dev = static_cast<const double*>(xyz), *cov_dev = static_cast<const double*>(cov);
-  if (!from_device) {            // covariance rows first: 48 n bytes keep the landmark rows 16-byte aligned
+  if (!from_device) {
     SBA_TRY_HIP(staging.alloc(9 * n * sizeof(double)));
-    double* s = staging.as<double>();
-    SBA_TRY_HIP(hipMemcpyAsync(s, cov, 6 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    SBA_TRY_HIP(hipMemcpyAsync(s + 6 * n, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    cov_dev = s; xyz_dev = s + 6 * n;
+    rc = stage_rows_up(h, staging.as<double>(), xyz, cov, n);
+    if (rc) return rc;
+    cov_dev = staging.as<double>(); xyz_dev = cov_dev + 6 * n;
   }
   int occ = 1;
-  int rc = pack_occ(h, false, &occ);
+  rc = pack_occ(h, false, &occ);
   if (rc) return rc;
   const sba::LandmarkPlanes pl{h->planes, elems};
   SBA_TRY_HIP(sba::launch_landmarks_pack(xyz_dev, cov_dev, n, cov_scale, pl, grid_for(h, elems / 2, occ), h->stream));
@@ -115,8 +197,7 @@ int set_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n, dou
 int get_common(sba_landmarks* h, void* xyz, void* cov, bool to_device) {
   if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
   SBA_REFUSE_POISONED(h);
-  if (to_device && ((reinterpret_cast<uintptr_t>(xyz) | reinterpret_cast<uintptr_t>(cov)) & 15u))
-    return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
+  if (rows_unaligned(to_device, xyz, cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
   if (h->n == 0 || (!xyz && !cov)) return SBA_OK;
   SBA_TRY_HIP(hipSetDevice(h->device));
   const size_t n = h->n;
@@ -132,8 +213,8 @@ int get_common(sba_landmarks* h, void* xyz, void* cov, bool to_device) {
   SBA_TRY_HIP(staging.alloc(9 * n * sizeof(double)));
   double* s = staging.as<double>();
   SBA_TRY_HIP(sba::launch_landmarks_unpack(planes_of(h), n, xyz ? s + 6 * n : nullptr, cov ? s : nullptr, grid, h->stream));
-  if (cov) SBA_TRY_HIP(hipMemcpyAsync(cov, s, 6 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (xyz) SBA_TRY_HIP(hipMemcpyAsync(xyz, s + 6 * n, 3 * n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  rc = stage_rows_down(h, s, n, xyz, cov);
+  if (rc) return rc;
   return sba::stream_wait(h->stream, "landmark unpack", &h->poisoned);
 }
 
@@ -232,43 +313,26 @@ int sba_landmarks_fuse(sba_landmarks* h, const int64_t* idx, const double* beari
   *res = sba_landmark_fuse_result{};
   if (h->n == 0 || m == 0) return SBA_OK;
   SBA_TRY_HIP(hipSetDevice(h->device));
-  // counters | chi2 [elems] | bearings [elems][3] | idx [elems]: every part starts 16-byte aligned (elems is even)
-  const size_t elems = h->elems, need = 32 + elems * 5 * sizeof(double);
-  if (h->obs_bytes < need) {
-    if (h->obs) SBA_TRY_HIP(hipFree(h->obs));
-    h->obs = nullptr; h->obs_bytes = 0;
-    SBA_TRY_HIP(hipMalloc(&h->obs, need));
-    h->obs_bytes = need;
-  }
-  unsigned long long* counters = static_cast<unsigned long long*>(h->obs);
-  double* chi2_dev = reinterpret_cast<double*>(counters + 4);
-  double* bearings_dev = chi2_dev + elems;
-  long long* idx_dev = reinterpret_cast<long long*>(bearings_dev + 3 * elems);
-  static_assert(sba::LANDMARK_CLASSES == 4 && sizeof(long long) == sizeof(int64_t), "layout of the observation scratch");
-  SBA_TRY_HIP(hipMemcpyAsync(bearings_dev, bearings, 3 * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (idx) SBA_TRY_HIP(hipMemcpyAsync(idx_dev, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  else if (elems > m) SBA_TRY_HIP(hipMemsetAsync(bearings_dev + 3 * m, 0, 3 * (elems - m) * sizeof(double), h->stream));   // the padding row: not seen
+  ObsScratch obs;
+  int rc = obs_scratch(h, false, &obs);
+  if (rc) return rc;
+  rc = upload_observations(h, obs, idx, bearings, m);
+  if (rc) return rc;
   sba::LandmarkFuseParams prm;
   sba::landmark_fuse_fill(h->n, m, rot, tran, opt->pose_cov, opt->bearing_sigma, opt->chi2_gate, &prm);
   const bool indexed = idx != nullptr, apply = opt->apply != 0;
-  int& occ = h->occ_fuse[indexed ? 1 : 0][apply ? 1 : 0];
-  if (occ == 0) {
-    SBA_TRY_HIP(sba::landmarks_fuse_blocks_per_cu(indexed, apply, &occ));
-    occ = std::max(1, occ);
-  }
-  const int grid = grid_for(h, indexed ? m : elems / 2, occ);
-  SBA_TRY_HIP(sba::launch_landmarks_fuse(planes_of(h), prm, indexed ? idx_dev : nullptr, bearings_dev, chi2_out ? chi2_dev : nullptr, counters, apply,
-                                         grid, h->stream));
-  unsigned long long host_counts[4] = {0, 0, 0, 0};
-  SBA_TRY_HIP(hipMemcpyAsync(host_counts, counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
-  if (chi2_out) SBA_TRY_HIP(hipMemcpyAsync(chi2_out, chi2_dev, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  const int rc = sba::stream_wait(h->stream, "landmark fusion pass", &h->poisoned);
+  int occ = 1;
+  rc = fuse_occ(h, indexed, apply, &occ);
   if (rc) return rc;
-  res->n_skipped = static_cast<long long>(host_counts[sba::LANDMARK_SKIPPED]);
-  res->n_behind = static_cast<long long>(host_counts[sba::LANDMARK_BEHIND]);
-  res->n_gated = static_cast<long long>(host_counts[sba::LANDMARK_GATED]);
-  res->n_fused = static_cast<long long>(host_counts[sba::LANDMARK_FUSED]);
-  res->n_obs = res->n_skipped + res->n_behind + res->n_gated + res->n_fused;
+  const int grid = grid_for(h, indexed ? m : h->elems / 2, occ);
+  SBA_TRY_HIP(sba::launch_landmarks_fuse(planes_of(h), prm, indexed ? obs.idx : nullptr, obs.bearings, chi2_out ? obs.chi2 : nullptr, obs.counters, apply,
+                                         grid, h->stream));
+  unsigned long long host_counts[sba::LANDMARK_CLASSES] = {0, 0, 0, 0};
+  SBA_TRY_HIP(hipMemcpyAsync(host_counts, obs.counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
+  if (chi2_out) SBA_TRY_HIP(hipMemcpyAsync(chi2_out, obs.chi2, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "landmark fusion pass", &h->poisoned);
+  if (rc) return rc;
+  counts_to_result(host_counts, res);
   return SBA_OK;
 }
 
@@ -279,36 +343,11 @@ namespace {
 
 size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
 
-int edit_occ(sba_landmarks* h, int which, int* occ) {
-  int& o = h->occ_edit[which];
-  if (o == 0) {
-    SBA_TRY_HIP(sba::landmarks_edit_blocks_per_cu(which, &o));
-    o = std::max(1, o);
-  }
-  *occ = o;
-  return SBA_OK;
-}
-
-// The scratch of one edit, at least `bytes`; what it held is lost when it grows.
-int edit_scratch(sba_landmarks* h, size_t bytes) {
-  if (h->edit_bytes >= bytes) return SBA_OK;
-  if (h->edit) SBA_TRY_HIP(hipFree(h->edit));
-  h->edit = nullptr; h->edit_bytes = 0;
-  SBA_TRY_HIP(hipMalloc(&h->edit, bytes));
-  h->edit_bytes = bytes;
-  return SBA_OK;
-}
+// The scratch of one edit, at least `bytes`.
+int edit_scratch(sba_landmarks* h, size_t bytes) { return grow_scratch(&h->edit, &h->edit_bytes, bytes); }
 
 // The other plane allocation, at least `bytes`: grown only when it is too small, then by half at least.
-int alt_planes(sba_landmarks* h, size_t bytes) {
-  if (h->planes_alt_bytes >= bytes) return SBA_OK;
-  const size_t cap = std::max(bytes, h->planes_alt_bytes + h->planes_alt_bytes / 2);
-  if (h->planes_alt) SBA_TRY_HIP(hipFree(h->planes_alt));
-  h->planes_alt = nullptr; h->planes_alt_bytes = 0;
-  SBA_TRY_HIP(hipMalloc(reinterpret_cast<void**>(&h->planes_alt), cap));
-  h->planes_alt_bytes = cap;
-  return SBA_OK;
-}
+int alt_planes(sba_landmarks* h, size_t bytes) { return grow_scratch(&h->planes_alt, &h->planes_alt_bytes, bytes, 2); }
 
 // The other allocation holds the map now: n landmarks at a stride of elems.
 void swap_planes(sba_landmarks* h, size_t n, size_t elems) {
@@ -321,8 +360,7 @@ int append_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n_a
   if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
   SBA_REFUSE_POISONED(h);
   if (n_add > 0 && (!xyz || !cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark or covariance array");
-  if (from_device && ((reinterpret_cast<uintptr_t>(xyz) | reinterpret_cast<uintptr_t>(cov)) & 15u))
-    return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
+  if (rows_unaligned(from_device, xyz, cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
   if (const char* why = sba::resect_weight_check_scale(cov_scale)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
   if (const char* why = sba::landmark_check_sizes(h->n, n_add)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (n = %zu, n_add = %zu)", why, h->n, n_add);
   if (n_add == 0) return SBA_OK;
@@ -331,13 +369,12 @@ int append_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n_a
   int rc = alt_planes(h, planes_size(elems_new));
   if (rc) return rc;
   const double *xyz_dev = static_cast<const double*>(xyz), *cov_dev = static_cast<const double*>(cov);
-  if (!from_device) {            // covariance rows first: 48 n_add bytes keep the landmark rows 16-byte aligned
+  if (!from_device) {
     rc = edit_scratch(h, 9 * n_add * sizeof(double));
     if (rc) return rc;
-    double* s = static_cast<double*>(h->edit);
-    SBA_TRY_HIP(hipMemcpyAsync(s, cov, 6 * n_add * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    SBA_TRY_HIP(hipMemcpyAsync(s + 6 * n_add, xyz, 3 * n_add * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    cov_dev = s; xyz_dev = s + 6 * n_add;
+    rc = stage_rows_up(h, static_cast<double*>(h->edit), xyz, cov, n_add);
+    if (rc) return rc;
+    cov_dev = static_cast<const double*>(h->edit); xyz_dev = cov_dev + 6 * n_add;
   }
   int occ = 1;
   rc = edit_occ(h, sba::LANDMARK_EDIT_APPEND, &occ);
@@ -353,8 +390,7 @@ int append_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n_a
 int gather_common(sba_landmarks* h, const int64_t* idx, size_t m, void* xyz, void* cov, uint32_t* counts, bool to_device) {
   if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
   SBA_REFUSE_POISONED(h);
-  if (to_device && ((reinterpret_cast<uintptr_t>(xyz) | reinterpret_cast<uintptr_t>(cov)) & 15u))
-    return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
+  if (rows_unaligned(to_device, xyz, cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
   if (const char* why = sba::landmark_check_sizes(0, m)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (m = %zu)", why, m);
   if (const char* why = sba::landmark_check_gather_index(idx, m, h->n)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (m = %zu, n = %zu)", why, m, h->n);
   if (m == 0 || (!xyz && !cov && !counts)) return SBA_OK;
@@ -366,8 +402,8 @@ int gather_common(sba_landmarks* h, const int64_t* idx, size_t m, void* xyz, voi
   long long* idx_dev = static_cast<long long*>(h->edit);
   double *cov_dev = static_cast<double*>(cov), *xyz_dev = static_cast<double*>(xyz);
   uint32_t* counts_dev = nullptr;
+  double* s = reinterpret_cast<double*>(idx_dev + m);      // the staged rows, when they go to the host
   if (!to_device) {
-    double* s = reinterpret_cast<double*>(idx_dev + m);
     cov_dev = cov ? s : nullptr;
     xyz_dev = xyz ? s + 6 * m : nullptr;
     counts_dev = counts ? reinterpret_cast<uint32_t*>(s + 9 * m) : nullptr;
@@ -378,8 +414,8 @@ int gather_common(sba_landmarks* h, const int64_t* idx, size_t m, void* xyz, voi
   if (rc) return rc;
   SBA_TRY_HIP(sba::launch_landmarks_gather(planes_of(h), idx_dev, m, xyz_dev, cov_dev, counts_dev, grid_for(h, m, occ), h->stream));
   if (!to_device) {
-    if (cov) SBA_TRY_HIP(hipMemcpyAsync(cov, cov_dev, 6 * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (xyz) SBA_TRY_HIP(hipMemcpyAsync(xyz, xyz_dev, 3 * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    rc = stage_rows_down(h, s, m, xyz, cov);
+    if (rc) return rc;
     if (counts) SBA_TRY_HIP(hipMemcpyAsync(counts, counts_dev, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   }
   return sba::stream_wait(h->stream, "landmark gather", &h->poisoned);
@@ -502,24 +538,12 @@ struct RegisterWork {
   bool indexed = false;
   size_t m = 0;
   double bearing_sigma = 0.0;
-  unsigned long long* counters = nullptr;      // the apply pass's class counts (observation scratch)
-  double *chi2_dev = nullptr, *bearings_dev = nullptr, *noise_dev = nullptr;
-  long long* idx_dev = nullptr;
+  ObsScratch obs;                              // its counters: the apply pass's class counts
   unsigned long long* freeze_counters = nullptr;
   double *row_dev = nullptr, *partials = nullptr;
   int grid_freeze = 0, grid_reduce = 0;
   long long freeze_counts[sba::LANDMARK_CLASSES] = {0, 0, 0, 0};
 };
-
-int register_occ(sba_landmarks* h, int which, bool indexed, bool apply, int* occ) {
-  int& o = h->occ_reg[which][indexed ? 1 : 0][apply ? 1 : 0];
-  if (o == 0) {
-    SBA_TRY_HIP(sba::landmarks_register_blocks_per_cu(which, indexed, apply, &o));
-    o = std::max(1, o);
-  }
-  *occ = o;
-  return SBA_OK;
-}
 
 // The refusals sba_landmarks_eval_register and sba_landmarks_register share, all before the first device call.
 int register_check(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double* rot, const double* tran,
@@ -539,26 +563,15 @@ int register_check(sba_landmarks* h, const int64_t* idx, const double* bearings,
 int register_freeze(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double rot_ref[3], const double tran_ref[3],
                     double bearing_sigma, RegisterWork* w) {
   SBA_TRY_HIP(hipSetDevice(h->device));
-  // counters | chi2 [elems] | bearings [elems][3] | idx [elems] | noise [elems]: sba_landmarks_fuse's layout, then the noise plane
-  const size_t elems = h->elems, need = 32 + elems * 6 * sizeof(double);
-  if (h->obs_bytes < need) {
-    if (h->obs) SBA_TRY_HIP(hipFree(h->obs));
-    h->obs = nullptr; h->obs_bytes = 0;
-    SBA_TRY_HIP(hipMalloc(&h->obs, need));
-    h->obs_bytes = need;
-  }
+  const size_t elems = h->elems;
+  int rc = obs_scratch(h, true, &w->obs);      // sba_landmarks_fuse's layout, then the noise plane; grow_scratch's hipMalloc: after hipSetDevice
+  if (rc) return rc;
   w->indexed = idx != nullptr;
   w->m = m;
   w->bearing_sigma = bearing_sigma;
-  w->counters = static_cast<unsigned long long*>(h->obs);
-  w->chi2_dev = reinterpret_cast<double*>(w->counters + 4);
-  w->bearings_dev = w->chi2_dev + elems;
-  w->idx_dev = reinterpret_cast<long long*>(w->bearings_dev + 3 * elems);
-  w->noise_dev = reinterpret_cast<double*>(w->idx_dev + elems);
-  static_assert(sba::LANDMARK_CLASSES == 4 && sizeof(long long) == sizeof(int64_t), "layout of the observation scratch");
   const size_t items = w->indexed ? m : elems / 2;
   int occ = 1;
-  int rc = register_occ(h, sba::LANDMARK_REGISTER_FREEZE, w->indexed, false, &occ);
+  rc = register_occ(h, sba::LANDMARK_REGISTER_FREEZE, w->indexed, false, &occ);
   if (rc) return rc;
   w->grid_freeze = grid_for(h, items, occ);
   // The reduce pass: two observations per lane in both forms and one grid rule for both (the smaller occupancy), so that the
@@ -569,25 +582,19 @@ int register_freeze(sba_landmarks* h, const int64_t* idx, const double* bearings
   rc = register_occ(h, sba::LANDMARK_REGISTER_REDUCE, !w->indexed, false, &occ_other);
   if (rc) return rc;
   w->grid_reduce = grid_for(h, w->indexed ? (m + 1) / 2 : elems / 2, std::min(occ, occ_other));
-  // freeze counters (32 B) | the folded row | block rows [grid]
-  const size_t reg_need = 32 + (static_cast<size_t>(w->grid_reduce) + 1) * sba::JOINT_ROW * sizeof(double);
-  if (h->reg_bytes < reg_need) {
-    if (h->reg) SBA_TRY_HIP(hipFree(h->reg));
-    h->reg = nullptr; h->reg_bytes = 0;
-    SBA_TRY_HIP(hipMalloc(&h->reg, reg_need));
-    h->reg_bytes = reg_need;
-  }
+  // freeze counters | the folded row | block rows [grid]
+  rc = grow_scratch(&h->reg, &h->reg_bytes, kCounterBytes + (static_cast<size_t>(w->grid_reduce) + 1) * sba::JOINT_ROW * sizeof(double));
+  if (rc) return rc;
   w->freeze_counters = static_cast<unsigned long long*>(h->reg);
-  w->row_dev = reinterpret_cast<double*>(w->freeze_counters + 4);
+  w->row_dev = reinterpret_cast<double*>(w->freeze_counters + sba::LANDMARK_CLASSES);
   w->partials = w->row_dev + sba::JOINT_ROW;
-  SBA_TRY_HIP(hipMemcpyAsync(w->bearings_dev, bearings, 3 * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (idx) SBA_TRY_HIP(hipMemcpyAsync(w->idx_dev, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  else if (elems > m) SBA_TRY_HIP(hipMemsetAsync(w->bearings_dev + 3 * m, 0, 3 * (elems - m) * sizeof(double), h->stream));   // the padding row: not seen
+  rc = upload_observations(h, w->obs, idx, bearings, m);
+  if (rc) return rc;
   sba::LandmarkRegisterParams prm;
   sba::landmark_register_fill(h->n, m, rot_ref, tran_ref, nullptr, bearing_sigma, INFINITY, &prm);
-  SBA_TRY_HIP(sba::launch_landmarks_register_freeze(planes_of(h), prm, w->indexed ? w->idx_dev : nullptr, w->bearings_dev, w->noise_dev,
+  SBA_TRY_HIP(sba::launch_landmarks_register_freeze(planes_of(h), prm, w->indexed ? w->obs.idx : nullptr, w->obs.bearings, w->obs.noise,
                                                     w->freeze_counters, w->grid_freeze, h->stream));
-  unsigned long long host_counts[4] = {0, 0, 0, 0};
+  unsigned long long host_counts[sba::LANDMARK_CLASSES] = {0, 0, 0, 0};
   SBA_TRY_HIP(hipMemcpyAsync(host_counts, w->freeze_counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
   rc = sba::stream_wait(h->stream, "landmark registration freeze", &h->poisoned);
   if (rc) return rc;
@@ -599,7 +606,7 @@ int register_freeze(sba_landmarks* h, const int64_t* idx, const double* bearings
 int register_reduce_pass(sba_landmarks* h, const RegisterWork& w, const double rot[3], const double tran[3], double* row) {
   sba::LandmarkRegisterParams prm;
   sba::landmark_register_fill(h->n, w.m, rot, tran, nullptr, w.bearing_sigma, INFINITY, &prm);
-  SBA_TRY_HIP(sba::launch_landmarks_register_reduce(planes_of(h), prm, w.indexed ? w.idx_dev : nullptr, w.bearings_dev, w.noise_dev, w.partials,
+  SBA_TRY_HIP(sba::launch_landmarks_register_reduce(planes_of(h), prm, w.indexed ? w.obs.idx : nullptr, w.obs.bearings, w.obs.noise, w.partials,
                                                     w.grid_reduce, w.row_dev, h->stream));
   SBA_TRY_HIP(hipMemcpyAsync(row, w.row_dev, SBA_RESECT_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   return sba::stream_wait(h->stream, "landmark registration reduce pass", &h->poisoned);
@@ -687,21 +694,17 @@ int sba_landmarks_register(sba_landmarks* h, const int64_t* idx, const double* b
   if (rc) return rc;
   sba::LandmarkRegisterParams prm;
   sba::landmark_register_fill(h->n, m, r, t, cov, opt->bearing_sigma, opt->chi2_gate, &prm);
-  SBA_TRY_HIP(sba::launch_landmarks_register_apply(planes_of(h), prm, w.indexed ? w.idx_dev : nullptr, w.bearings_dev, w.noise_dev,
-                                                   chi2_out ? w.chi2_dev : nullptr, w.counters, apply,
+  SBA_TRY_HIP(sba::launch_landmarks_register_apply(planes_of(h), prm, w.indexed ? w.obs.idx : nullptr, w.obs.bearings, w.obs.noise,
+                                                   chi2_out ? w.obs.chi2 : nullptr, w.obs.counters, apply,
                                                    grid_for(h, w.indexed ? m : h->elems / 2, occ), h->stream));
-  unsigned long long host_counts[4] = {0, 0, 0, 0};
-  SBA_TRY_HIP(hipMemcpyAsync(host_counts, w.counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
-  if (chi2_out) SBA_TRY_HIP(hipMemcpyAsync(chi2_out, w.chi2_dev, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  unsigned long long host_counts[sba::LANDMARK_CLASSES] = {0, 0, 0, 0};
+  SBA_TRY_HIP(hipMemcpyAsync(host_counts, w.obs.counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
+  if (chi2_out) SBA_TRY_HIP(hipMemcpyAsync(chi2_out, w.obs.chi2, m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   rc = sba::stream_wait(h->stream, "landmark registration write-back", &h->poisoned);
   if (rc) return rc;
   for (int a = 0; a < 3; ++a) { res->rot[a] = r[a]; res->tran[a] = t[a]; }
   std::memcpy(res->cov, cov, sizeof(cov));
-  res->n_skipped = static_cast<long long>(host_counts[sba::LANDMARK_SKIPPED]);
-  res->n_behind = static_cast<long long>(host_counts[sba::LANDMARK_BEHIND]);
-  res->n_gated = static_cast<long long>(host_counts[sba::LANDMARK_GATED]);
-  res->n_fused = static_cast<long long>(host_counts[sba::LANDMARK_FUSED]);
-  res->n_obs = res->n_skipped + res->n_behind + res->n_gated + res->n_fused;
+  counts_to_result(host_counts, res);
   res->n_used = static_cast<long long>(at->n_used);
   sum.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
   res->summary = sum;

@@ -3,33 +3,18 @@
 // allocation, then one u32 plane of accepted observations; elems = n rounded up to a whole 16-byte vector, zeros beyond n.
 //   landmarks_pack_kernel      caller rows [n][3] + [n][6] -> the planes, cov_scale applied, counts zeroed, padding zeroed
 //   landmarks_unpack_kernel    the planes -> caller rows, exactly n of each
-//   landmarks_fuse_kernel<INDEXED, APPLY>
-//       dense:   lane p owns landmarks 2 p and 2 p + 1: nine 16-byte plane loads, three 16-byte loads of its 48 bytes of
-//                bearing rows, nine 16-byte stores when one of its two landmarks was fused, one 16-byte store of chi2
-//       indexed: lane j owns observation j and gathers landmark idx[j] (sorted: neighbouring lanes, neighbouring lines)
-//       APPLY = false: chi2 and counts only.
+//   landmarks_fuse_kernel<INDEXED, APPLY>   sba_landmarks_pass.inc around landmark_fuse_one: the dense and the indexed form and
+//                                           what APPLY = false leaves out are described there
 // All: 256-thread blocks, grid-stride, plain stores.  The pose, its covariance terms and the scalars are one by-value
-// argument (scalar registers).  Class counts: a ballot and a population count per class and step, one integer atomic per wave
-// and class at the end.  No floating-point reduction anywhere: the bytes do not depend on the grid.
+// argument (scalar registers).  No floating-point reduction anywhere: the bytes do not depend on the grid.
 // Bytes per landmark, dense: 72 + 4 (planes, count) + 24 (bearing) read, up to 72 + 4 + 8 written.
+// The plane accessors, the non-temporal load, the register block and the class counts: sba_landmarks_device.hpp (lm::).
 #include "sba_device.hpp"
 #include "sba_landmarks.hpp"
+#include "sba_landmarks_device.hpp"
 
 namespace sba {
 namespace {
-
-__device__ __forceinline__ double2 lm_load(const double2* ptr) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const f4 r = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ptr));
-  return *reinterpret_cast<const double2*>(&r);
-}
-
-__device__ __forceinline__ double2* lm_plane(double* base, unsigned long long elems, int k) {
-  return reinterpret_cast<double2*>(base + static_cast<size_t>(k) * elems);
-}
-__device__ __forceinline__ unsigned int* lm_counts(double* base, unsigned long long elems) {
-  return reinterpret_cast<unsigned int*>(base + 9 * static_cast<size_t>(elems));
-}
 
 __global__ __launch_bounds__(256) void landmarks_pack_kernel(const double* __restrict__ xyz, const double* __restrict__ cov, unsigned long long n,
                                                              double cov_scale, double* __restrict__ base, unsigned long long elems) {
@@ -43,11 +28,11 @@ __global__ __launch_bounds__(256) void landmarks_pack_kernel(const double* __res
     if (2 * p + 1 < n) {          // both rows exist: 48 + 96 contiguous bytes, 16-byte aligned
       const double2* xv = reinterpret_cast<const double2*>(xyz) + 3 * p;
       const double2* cv = reinterpret_cast<const double2*>(cov) + 6 * p;
-      const double2 x0 = lm_load(xv), x1 = lm_load(xv + 1), x2 = lm_load(xv + 2);
+      const double2 x0 = lm::load_nt(xv), x1 = lm::load_nt(xv + 1), x2 = lm::load_nt(xv + 2);
       v[0][0] = x0.x; v[0][1] = x0.y; v[0][2] = x1.x; v[1][0] = x1.y; v[1][1] = x2.x; v[1][2] = x2.y;
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        const double2 a = lm_load(cv + k), b = lm_load(cv + 3 + k);
+        const double2 a = lm::load_nt(cv + k), b = lm::load_nt(cv + 3 + k);
         v[0][3 + 2 * k] = a.x; v[0][4 + 2 * k] = a.y; v[1][3 + 2 * k] = b.x; v[1][4 + 2 * k] = b.y;
       }
     } else if (2 * p < n) {       // the last row of an odd n: nothing is read beyond the caller's rows
@@ -57,10 +42,10 @@ __global__ __launch_bounds__(256) void landmarks_pack_kernel(const double* __res
       for (int k = 0; k < 6; ++k) v[0][3 + k] = cov[12 * p + k];
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) lm_plane(base, elems, k)[p] = make_double2(v[0][k], v[1][k]);
+    for (int k = 0; k < 3; ++k) lm::plane(base, elems, k)[p] = make_double2(v[0][k], v[1][k]);
 #pragma unroll
-    for (int k = 3; k < 9; ++k) lm_plane(base, elems, k)[p] = make_double2(cov_scale * v[0][k], cov_scale * v[1][k]);
-    reinterpret_cast<uint2*>(lm_counts(base, elems))[p] = make_uint2(0u, 0u);
+    for (int k = 3; k < 9; ++k) lm::plane(base, elems, k)[p] = make_double2(cov_scale * v[0][k], cov_scale * v[1][k]);
+    reinterpret_cast<uint2*>(lm::counts(base, elems))[p] = make_uint2(0u, 0u);
   }
 }
 
@@ -70,7 +55,7 @@ __global__ __launch_bounds__(256) void landmarks_unpack_kernel(double* __restric
   for (size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < nvec; p += stride) {
     double2 v[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) v[k] = lm_plane(base, elems, k)[p];
+    for (int k = 0; k < 9; ++k) v[k] = lm::plane(base, elems, k)[p];
     const bool both = 2 * p + 1 < n;
     if (xyz) {
       if (both) {
@@ -96,97 +81,15 @@ __global__ __launch_bounds__(256) void landmarks_unpack_kernel(double* __restric
   }
 }
 
-// Four wave-uniform class counts: every active lane adds the same population counts.
-struct ClassCounts {
-  unsigned long long c[LANDMARK_CLASSES];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int k = 0; k < LANDMARK_CLASSES; ++k) c[k] = 0;
-  }
-  __device__ __forceinline__ void add(bool valid, int cls) {
-#pragma unroll
-    for (int k = 0; k < LANDMARK_CLASSES; ++k) c[k] += __popcll(__ballot(valid && cls == k));
-  }
-  // Lanes of a wave hold consecutive items, so lane 0 took part in every step any lane of its wave took part in.
-  __device__ __forceinline__ void flush(unsigned long long* __restrict__ counters) const {
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int k = 0; k < LANDMARK_CLASSES; ++k)
-        if (c[k] != 0) atomicAdd(counters + k, c[k]);
-    }
-  }
-};
-
 template <bool INDEXED, bool APPLY>
 __global__ __launch_bounds__(256) void landmarks_fuse_kernel(LandmarkFuseParams P, double* __restrict__ base, unsigned long long elems,
                                                              const long long* __restrict__ idx, const double* __restrict__ bearings,
                                                              double* __restrict__ chi2, unsigned long long* __restrict__ counters) {
-  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  ClassCounts cc;
-  cc.init();
-  if (INDEXED) {
-    const size_t m = P.m;
-    for (size_t j = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < m; j += stride) {
-      const size_t i = static_cast<size_t>(idx[j]);        // < n: validated on the host
-      double X[3], Sg[6], y[3], Xo[3], So[6], s;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { X[k] = base[static_cast<size_t>(k) * elems + i]; y[k] = bearings[3 * j + k]; }
-#pragma unroll
-      for (int k = 0; k < 6; ++k) Sg[k] = base[static_cast<size_t>(3 + k) * elems + i];
-      const int cls = landmark_fuse_one(P, X, Sg, y, Xo, So, &s);
-      cc.add(true, cls);
-      if (chi2) chi2[j] = s;
-      if (APPLY && cls == LANDMARK_FUSED) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) base[static_cast<size_t>(k) * elems + i] = Xo[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) base[static_cast<size_t>(3 + k) * elems + i] = So[k];
-        lm_counts(base, elems)[i] += 1u;
-      }
-    }
-  } else {
-    const size_t n = P.n, nvec = (n + 1) / 2;
-    for (size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < nvec; p += stride) {
-      double2 v[9], yv[3];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) v[k] = lm_load(lm_plane(base, elems, k) + p);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) yv[k] = lm_load(reinterpret_cast<const double2*>(bearings) + 3 * p + k);
-      const double yr[2][3] = {{yv[0].x, yv[0].y, yv[1].x}, {yv[1].y, yv[2].x, yv[2].y}};
-      double s[2];
-      bool fused[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool valid = 2 * p + h < n;
-        double X[3], Sg[6], Xo[3], So[6];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) X[k] = h == 0 ? v[k].x : v[k].y;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) Sg[k] = h == 0 ? v[3 + k].x : v[3 + k].y;
-        const int cls = landmark_fuse_one(P, X, Sg, yr[h], Xo, So, &s[h]);
-        cc.add(valid, cls);
-        fused[h] = valid && cls == LANDMARK_FUSED;
-        if (APPLY && fused[h]) {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) { if (h == 0) v[k].x = Xo[k]; else v[k].y = Xo[k]; }
-#pragma unroll
-          for (int k = 0; k < 6; ++k) { if (h == 0) v[3 + k].x = So[k]; else v[3 + k].y = So[k]; }
-        }
-        __builtin_amdgcn_sched_barrier(0);     // one landmark at a time: the second one's temporaries reuse the first one's registers
-      }
-      if (chi2) reinterpret_cast<double2*>(chi2)[p] = make_double2(s[0], s[1]);
-      if (APPLY && (fused[0] || fused[1])) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) lm_plane(base, elems, k)[p] = v[k];
-        uint2* cp = reinterpret_cast<uint2*>(lm_counts(base, elems)) + p;
-        uint2 c = *cp;
-        c.x += fused[0] ? 1u : 0u;
-        c.y += fused[1] ? 1u : 0u;
-        *cp = c;
-      }
-    }
-  }
-  cc.flush(counters);
+  constexpr bool NOISE = false;
+  const double* noise = nullptr;          // no noise plane: never read
+#define SBA_LANDMARK_PASS_ONE(X, Sg, y, nz, Xo, So, chi2) landmark_fuse_one(P, X, Sg, y, Xo, So, chi2)
+#include "sba_landmarks_pass.inc"
+#undef SBA_LANDMARK_PASS_ONE
 }
 
 const void* fuse_kernel_of(bool indexed, bool apply) {

@@ -3,9 +3,8 @@
 // planes of `elems` doubles in one allocation, then one u32 plane of counts; elems = n rounded up to even, zeros beyond n.
 //   landmarks_scores_kernel           lane p owns landmarks 2 p and 2 p + 1: nine 16-byte plane loads, one 16-byte store
 //   landmarks_keep_kernel             the same nine loads plus the two counts and two mask bytes; two keep bytes per lane, whole
-//                                     tiles of kCompactTile bytes, zero beyond n; five class counts: a ballot and a population
-//                                     count per class and step, one integer atomic per wave and class at the end, spread over
-//                                     64 counter rows that the host sums
+//                                     tiles of kCompactTile bytes, zero beyond n; five class counts, flushed over the
+//                                     kLandmarkCounterRows counter rows that the host sums
 //   landmarks_compact_scatter_kernel  block b = tile b: rank within the tile by ballot and mbcnt, per-wave prefixes in LDS (as
 //                                     compact_scatter_kernel of sba_select.hip); the ten planes of a kept landmark go to
 //                                     tile_offset + rank of ANOTHER allocation (in place a tile's destinations lie in the source
@@ -17,34 +16,23 @@
 // All: 256-thread blocks, plain stores; grid-stride except the scatter (one block per tile).  No floating-point reduction
 // anywhere: the bytes do not depend on the grid.
 // Bytes per landmark: keep 72 + 4 (+ 1 mask) read, 1 written; scatter 1 + 76 read and 76 + 8 written per kept landmark.
+// The plane accessors, the two-landmark register block and the class counts: sba_landmarks_device.hpp (lm::).
 #include "sba_device.hpp"
+#include "sba_landmarks_device.hpp"
 #include "sba_landmarks_edit.hpp"
 
 namespace sba {
 namespace {
 
-__device__ __forceinline__ double2 lme_load(const double2* ptr) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const f4 r = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ptr));
-  return *reinterpret_cast<const double2*>(&r);
-}
-
-__device__ __forceinline__ double2* lme_plane(double* base, unsigned long long elems, int k) {
-  return reinterpret_cast<double2*>(base + static_cast<size_t>(k) * elems);
-}
-__device__ __forceinline__ unsigned int* lme_counts(double* base, unsigned long long elems) {
-  return reinterpret_cast<unsigned int*>(base + 9 * static_cast<size_t>(elems));
-}
-
 __global__ __launch_bounds__(256) void landmarks_scores_kernel(double* __restrict__ base, unsigned long long elems, double* __restrict__ out) {
   const size_t nvec = elems / 2, stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < nvec; p += stride) {
-    double2 v[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) v[k] = lme_load(lme_plane(base, elems, k) + p);
-    const double X0[3] = {v[0].x, v[1].x, v[2].x}, X1[3] = {v[0].y, v[1].y, v[2].y};
-    const double S0[6] = {v[3].x, v[4].x, v[5].x, v[6].x, v[7].x, v[8].x}, S1[6] = {v[3].y, v[4].y, v[5].y, v[6].y, v[7].y, v[8].y};
-    reinterpret_cast<double2*>(out)[p] = make_double2(landmark_score(X0, S0), landmark_score(X1, S1));
+    lm::PairRegs<false> cur;
+    double X[2][3], S[2][6];
+    cur.load_planes(base, elems, p);
+    cur.landmark(0, X[0], S[0]);
+    cur.landmark(1, X[1], S[1]);
+    reinterpret_cast<double2*>(out)[p] = make_double2(landmark_score(X[0], S[0]), landmark_score(X[1], S[1]));
   }
 }
 
@@ -55,36 +43,28 @@ __global__ __launch_bounds__(256) void landmarks_keep_kernel(double* __restrict_
                                                              unsigned char* __restrict__ keep, unsigned long long tile_pairs,
                                                              unsigned long long* __restrict__ counters) {
   const size_t nvec = elems / 2, stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  unsigned long long cc[LANDMARK_PRUNE_CLASSES];
-#pragma unroll
-  for (int k = 0; k < LANDMARK_PRUNE_CLASSES; ++k) cc[k] = 0;
+  lm::ClassCounts<LANDMARK_PRUNE_CLASSES> cc;
+  cc.init();
   for (size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < tile_pairs; p += stride) {
     int cls[2] = {LANDMARK_INVALID, LANDMARK_INVALID};
     const bool valid[2] = {2 * p < n, 2 * p + 1 < n};
     if (p < nvec) {
-      double2 v[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) v[k] = lme_load(lme_plane(base, elems, k) + p);
-      const uint2 c = reinterpret_cast<const uint2*>(lme_counts(base, elems))[p];
+      lm::PairRegs<false> cur;
+      double X[2][3], S[2][6];
+      cur.load_planes(base, elems, p);
+      const uint2 c = reinterpret_cast<const uint2*>(lm::counts(base, elems))[p];
       const unsigned short mb = mask ? reinterpret_cast<const unsigned short*>(mask)[p] : static_cast<unsigned short>(0x0101u);
-      const double X0[3] = {v[0].x, v[1].x, v[2].x}, X1[3] = {v[0].y, v[1].y, v[2].y};
-      const double S0[6] = {v[3].x, v[4].x, v[5].x, v[6].x, v[7].x, v[8].x}, S1[6] = {v[3].y, v[4].y, v[5].y, v[6].y, v[7].y, v[8].y};
-      cls[0] = landmark_prune_class(X0, S0, c.x, static_cast<unsigned char>(mb & 0xffu), max_score, min_count);
-      cls[1] = landmark_prune_class(X1, S1, c.y, static_cast<unsigned char>(mb >> 8), max_score, min_count);
+      cur.landmark(0, X[0], S[0]);
+      cur.landmark(1, X[1], S[1]);
+      cls[0] = landmark_prune_class(X[0], S[0], c.x, static_cast<unsigned char>(mb & 0xffu), max_score, min_count);
+      cls[1] = landmark_prune_class(X[1], S[1], c.y, static_cast<unsigned char>(mb >> 8), max_score, min_count);
     }
     const unsigned k0 = valid[0] && cls[0] == LANDMARK_KEPT ? 1u : 0u, k1 = valid[1] && cls[1] == LANDMARK_KEPT ? 1u : 0u;
     reinterpret_cast<unsigned short*>(keep)[p] = static_cast<unsigned short>(k0 | (k1 << 8));
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int k = 0; k < LANDMARK_PRUNE_CLASSES; ++k) cc[k] += __popcll(__ballot(valid[h] && cls[h] == k));
+    cc.add(valid[0], cls[0]);
+    cc.add(valid[1], cls[1]);
   }
-  if ((threadIdx.x & 63) == 0) {     // one of kLandmarkCounterRows rows per wave: all waves on the same five words serialise
-    unsigned long long* row = counters + static_cast<size_t>((blockIdx.x * 4u + (threadIdx.x >> 6)) % kLandmarkCounterRows) * kLandmarkCounterStride;
-#pragma unroll
-    for (int k = 0; k < LANDMARK_PRUNE_CLASSES; ++k)
-      if (cc[k] != 0) atomicAdd(row + k, cc[k]);
-  }
+  cc.flush_rows(counters);
 }
 
 // Block b = tile b.  Round r: thread t looks at landmark b * kCompactTile + r * 256 + t; a kept one goes to tile_offset[b] + (kept
@@ -102,7 +82,7 @@ __global__ __launch_bounds__(256) void landmarks_compact_scatter_kernel(const un
   // the padding row of an odd kept count: no kept landmark lands there
   if (dst && blockIdx.x == 0 && threadIdx.x < 10 && (n_kept & 1ull)) {
     if (threadIdx.x < 9) dst[static_cast<size_t>(threadIdx.x) * dst_elems + n_kept] = 0.0;
-    else lme_counts(dst, dst_elems)[n_kept] = 0u;
+    else lm::counts(dst, dst_elems)[n_kept] = 0u;
   }
   for (int r = 0; r < kCompactTile / 256; ++r) {
     const size_t i = tile0 + static_cast<size_t>(r) * 256 + threadIdx.x;
@@ -123,7 +103,7 @@ __global__ __launch_bounds__(256) void landmarks_compact_scatter_kernel(const un
       if (dst) {
 #pragma unroll
         for (int c = 0; c < 9; ++c) dst[static_cast<size_t>(c) * dst_elems + o] = src[static_cast<size_t>(c) * src_elems + i];
-        lme_counts(dst, dst_elems)[o] = reinterpret_cast<const unsigned int*>(src + 9 * static_cast<size_t>(src_elems))[i];
+        lm::counts(dst, dst_elems)[o] = lm::counts(src, src_elems)[i];
       }
       if (kept_index) kept_index[o] = static_cast<long long>(i);
     }
@@ -146,21 +126,21 @@ __global__ __launch_bounds__(256) void landmarks_append_kernel(const double* __r
     if (2 * p + 1 < n_old) {                 // two old rows: p lies within the old planes
 #pragma unroll
       for (int k = 0; k < 9; ++k) {
-        const double2 a = reinterpret_cast<const double2*>(src + static_cast<size_t>(k) * src_elems)[p];
+        const double2 a = lm::plane(src, src_elems, k)[p];
         v[0][k] = a.x; v[1][k] = a.y;
       }
-      const uint2 c = reinterpret_cast<const uint2*>(src + 9 * static_cast<size_t>(src_elems))[p];
+      const uint2 c = reinterpret_cast<const uint2*>(lm::counts(src, src_elems))[p];
       cnt[0] = c.x; cnt[1] = c.y;
     } else if (2 * p >= n_old && 2 * p + 1 < n_new && (n_old & 1ull) == 0) {
       // two new rows of an even old size: 48 + 96 contiguous bytes, 16-byte aligned as the caller's rows are
       const size_t q = p - n_old / 2;
       const double2* xv = reinterpret_cast<const double2*>(xyz) + 3 * q;
       const double2* cv = reinterpret_cast<const double2*>(cov) + 6 * q;
-      const double2 x0 = lme_load(xv), x1 = lme_load(xv + 1), x2 = lme_load(xv + 2);
+      const double2 x0 = lm::load_nt(xv), x1 = lm::load_nt(xv + 1), x2 = lm::load_nt(xv + 2);
       v[0][0] = x0.x; v[0][1] = x0.y; v[0][2] = x1.x; v[1][0] = x1.y; v[1][1] = x2.x; v[1][2] = x2.y;
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        const double2 a = lme_load(cv + k), b = lme_load(cv + 3 + k);
+        const double2 a = lm::load_nt(cv + k), b = lm::load_nt(cv + 3 + k);
         v[0][3 + 2 * k] = cov_scale * a.x; v[0][4 + 2 * k] = cov_scale * a.y;
         v[1][3 + 2 * k] = cov_scale * b.x; v[1][4 + 2 * k] = cov_scale * b.y;
       }
@@ -171,7 +151,7 @@ __global__ __launch_bounds__(256) void landmarks_append_kernel(const double* __r
         if (i < n_old) {
 #pragma unroll
           for (int k = 0; k < 9; ++k) v[h][k] = src[static_cast<size_t>(k) * src_elems + i];
-          cnt[h] = reinterpret_cast<const unsigned int*>(src + 9 * static_cast<size_t>(src_elems))[i];
+          cnt[h] = lm::counts(src, src_elems)[i];
         } else if (i < n_new) {
           const size_t j = i - n_old;
 #pragma unroll
@@ -182,8 +162,8 @@ __global__ __launch_bounds__(256) void landmarks_append_kernel(const double* __r
       }
     }
 #pragma unroll
-    for (int k = 0; k < 9; ++k) lme_plane(dst, dst_elems, k)[p] = make_double2(v[0][k], v[1][k]);
-    reinterpret_cast<uint2*>(lme_counts(dst, dst_elems))[p] = make_uint2(cnt[0], cnt[1]);
+    for (int k = 0; k < 9; ++k) lm::plane(dst, dst_elems, k)[p] = make_double2(v[0][k], v[1][k]);
+    reinterpret_cast<uint2*>(lm::counts(dst, dst_elems))[p] = make_uint2(cnt[0], cnt[1]);
   }
 }
 
@@ -202,7 +182,7 @@ __global__ __launch_bounds__(256) void landmarks_gather_kernel(const double* __r
 #pragma unroll
       for (int k = 0; k < 6; ++k) cov[6 * j + k] = base[static_cast<size_t>(3 + k) * elems + i];
     }
-    if (counts) counts[j] = reinterpret_cast<const unsigned int*>(base + 9 * static_cast<size_t>(elems))[i];
+    if (counts) counts[j] = lm::counts(base, elems)[i];
   }
 }
 

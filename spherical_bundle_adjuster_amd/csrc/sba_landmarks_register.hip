@@ -9,107 +9,44 @@
 //                                                     sums of the SBA_RESECT_* row; resect_block_fold to a block row of JOINT_ROW,
 //                                                     then the joint solve's finalize
 //   landmarks_register_apply_kernel<INDEXED, APPLY>   the write-back at the solution with Sigma_c: X+, Sigma+, the count, chi2 and
-//                                                     the class counts; APPLY = false: chi2 and counts only
+//                                                     the class counts; APPLY = false: chi2 and counts only.  The body is
+//                                                     sba_landmarks_pass.inc around landmark_register_one: the fusion's, with the noise
 // dense:   lane p owns landmarks 2 p and 2 p + 1 through 16-byte plane vectors; the reduce pass keeps the next step's vectors in
 //          registers and every pass takes one landmark at a time (sched_barrier)
 // indexed: lane j owns observation j and gathers landmark idx[j] (sorted: neighbouring lanes, neighbouring lines); in the reduce
 //          pass lane p owns observations 2 p and 2 p + 1, the dense form's order of summation, so that idx = 0 .. n - 1 returns
 //          the dense form's bits
 // All: 256-thread blocks, grid-stride, plain stores, no floating-point atomics.  The reduce pass is bit-identical run to run at
-// a fixed grid; the two passes without a reduction do not depend on the grid at all.  Class counts: a ballot and a population
-// count per class and step, one integer atomic per wave and class at the end.
+// a fixed grid; the two passes without a reduction do not depend on the grid at all.  The register block of a dense lane
+// (lm::PairRegs), the indexed gather and the class counts (lm::ClassCounts): sba_landmarks_device.hpp.
 #include "sba_device.hpp"
+#include "sba_landmarks_device.hpp"
 #include "sba_landmarks_register.hpp"
 #include "sba_resection_core.hpp"
 
 namespace sba {
 namespace {
 
-__device__ __forceinline__ double2 lr_load(const double2* ptr) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const f4 r = __builtin_nontemporal_load(reinterpret_cast<const f4*>(ptr));
-  return *reinterpret_cast<const double2*>(&r);
-}
-
-__device__ __forceinline__ double2* lr_plane(double* base, unsigned long long elems, int k) {
-  return reinterpret_cast<double2*>(base + static_cast<size_t>(k) * elems);
-}
-__device__ __forceinline__ unsigned int* lr_counts(double* base, unsigned long long elems) {
-  return reinterpret_cast<unsigned int*>(base + 9 * static_cast<size_t>(elems));
-}
-
-// Four wave-uniform class counts: every active lane adds the same population counts (as in sba_landmarks.hip).
-struct RegisterCounts {
-  unsigned long long c[LANDMARK_CLASSES];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int k = 0; k < LANDMARK_CLASSES; ++k) c[k] = 0;
-  }
-  __device__ __forceinline__ void add(bool valid, int cls) {
-#pragma unroll
-    for (int k = 0; k < LANDMARK_CLASSES; ++k) c[k] += __popcll(__ballot(valid && cls == k));
-  }
-  // Lanes of a wave hold consecutive items, so lane 0 took part in every step any lane of its wave took part in.
-  __device__ __forceinline__ void flush(unsigned long long* __restrict__ counters) const {
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int k = 0; k < LANDMARK_CLASSES; ++k)
-        if (c[k] != 0) atomicAdd(counters + k, c[k]);
-    }
-  }
-};
-
-// One 16-byte vector (two landmarks) of everything a dense pass reads: nine planes, 48 bytes of bearing rows, the noise.
-template <bool NOISE>
-struct RegisterRegs {
-  double2 v[9], yv[3], nz;
-  __device__ __forceinline__ void load(double* base, unsigned long long elems, const double* bearings, const double* noise, size_t p) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) v[k] = lr_load(lr_plane(base, elems, k) + p);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) yv[k] = lr_load(reinterpret_cast<const double2*>(bearings) + 3 * p + k);
-    if (NOISE) nz = lr_load(reinterpret_cast<const double2*>(noise) + p);
-  }
-  __device__ __forceinline__ void get(int h, double X[3], double Sg[6], double y[3]) const {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) X[k] = h == 0 ? v[k].x : v[k].y;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Sg[k] = h == 0 ? v[3 + k].x : v[3 + k].y;
-    y[0] = h == 0 ? yv[0].x : yv[1].y;
-    y[1] = h == 0 ? yv[0].y : yv[2].x;
-    y[2] = h == 0 ? yv[1].x : yv[2].y;
-  }
-};
-
-// Observation j of the indexed form: landmark idx[j] gathered from the planes, bearing row j.
-__device__ __forceinline__ void lr_gather(const double* base, unsigned long long elems, size_t i, const double* bearings, size_t j, double X[3],
-                                          double Sg[6], double y[3]) {
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { X[k] = base[static_cast<size_t>(k) * elems + i]; y[k] = bearings[3 * j + k]; }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) Sg[k] = base[static_cast<size_t>(3 + k) * elems + i];
-}
-
 template <bool INDEXED>
 __global__ __launch_bounds__(256) void landmarks_register_freeze_kernel(LandmarkRegisterParams P, double* __restrict__ base, unsigned long long elems,
                                                                         const long long* __restrict__ idx, const double* __restrict__ bearings,
                                                                         double* __restrict__ noise, unsigned long long* __restrict__ counters) {
   const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  RegisterCounts cc;
+  lm::ClassCounts<LANDMARK_CLASSES> cc;
   cc.init();
   if (INDEXED) {
     const size_t m = P.m;
     for (size_t j = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < m; j += stride) {
       const size_t i = static_cast<size_t>(idx[j]);        // < n: validated on the host
       double X[3], Sg[6], y[3], s2;
-      lr_gather(base, elems, i, bearings, j, X, Sg, y);
+      lm::gather(base, elems, i, bearings, j, X, Sg, y);
       cc.add(true, landmark_register_noise(P, X, Sg, y, &s2));
       noise[j] = s2;
     }
   } else {
     const size_t n = P.n, nvec = (n + 1) / 2;
     for (size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < nvec; p += stride) {
-      RegisterRegs<false> cur;
+      lm::PairRegs<false> cur;
       cur.load(base, elems, bearings, nullptr, p);
       double s2[2];
 #pragma unroll
@@ -149,7 +86,7 @@ __global__ __launch_bounds__(256) void landmarks_register_reduce_kernel(Landmark
         const size_t j = valid ? 2 * p + h : 0;            // an odd m: the last lane's second slot re-reads observation 0 and drops it
         const size_t i = static_cast<size_t>(idx[j]);      // < n: validated on the host
         double X[3], Sg[6], y[3];
-        lr_gather(base, elems, i, bearings, j, X, Sg, y);
+        lm::gather(base, elems, i, bearings, j, X, Sg, y);
         const double s2 = noise[j];
         landmark_register_accumulate(P, X, Sg, y, s2, valid && landmark_register_live(s2), acc);
         __builtin_amdgcn_sched_barrier(0);                 // one observation at a time
@@ -158,7 +95,7 @@ __global__ __launch_bounds__(256) void landmarks_register_reduce_kernel(Landmark
   } else {
     const size_t n = P.n, nvec = (n + 1) / 2;
     size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    RegisterRegs<true> cur, nxt;
+    lm::PairRegs<true> cur, nxt;
     if (p < nvec) cur.load(base, elems, bearings, noise, p);
     while (p < nvec) {
       const size_t pn = p + stride;
@@ -167,7 +104,7 @@ __global__ __launch_bounds__(256) void landmarks_register_reduce_kernel(Landmark
       for (int h = 0; h < 2; ++h) {
         double X[3], Sg[6], y[3];
         cur.get(h, X, Sg, y);
-        const double s2 = h == 0 ? cur.nz.x : cur.nz.y;
+        const double s2 = cur.noise(h);
         landmark_register_accumulate(P, X, Sg, y, s2, 2 * p + h < n && landmark_register_live(s2), acc);
         __builtin_amdgcn_sched_barrier(0);                 // one landmark at a time, as in resect_wreduce_kernel
       }
@@ -183,62 +120,10 @@ __global__ __launch_bounds__(256) void landmarks_register_apply_kernel(LandmarkR
                                                                        const long long* __restrict__ idx, const double* __restrict__ bearings,
                                                                        const double* __restrict__ noise, double* __restrict__ chi2,
                                                                        unsigned long long* __restrict__ counters) {
-  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  RegisterCounts cc;
-  cc.init();
-  if (INDEXED) {
-    const size_t m = P.m;
-    for (size_t j = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; j < m; j += stride) {
-      const size_t i = static_cast<size_t>(idx[j]);        // < n: validated on the host
-      double X[3], Sg[6], y[3], Xo[3], So[6], s;
-      lr_gather(base, elems, i, bearings, j, X, Sg, y);
-      const int cls = landmark_register_one(P, X, Sg, y, noise[j], Xo, So, &s);
-      cc.add(true, cls);
-      if (chi2) chi2[j] = s;
-      if (APPLY && cls == LANDMARK_FUSED) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) base[static_cast<size_t>(k) * elems + i] = Xo[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) base[static_cast<size_t>(3 + k) * elems + i] = So[k];
-        lr_counts(base, elems)[i] += 1u;
-      }
-    }
-  } else {
-    const size_t n = P.n, nvec = (n + 1) / 2;
-    for (size_t p = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; p < nvec; p += stride) {
-      RegisterRegs<true> cur;
-      cur.load(base, elems, bearings, noise, p);
-      double s[2];
-      bool fused[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool valid = 2 * p + h < n;
-        double X[3], Sg[6], y[3], Xo[3], So[6];
-        cur.get(h, X, Sg, y);
-        const int cls = landmark_register_one(P, X, Sg, y, h == 0 ? cur.nz.x : cur.nz.y, Xo, So, &s[h]);
-        cc.add(valid, cls);
-        fused[h] = valid && cls == LANDMARK_FUSED;
-        if (APPLY && fused[h]) {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) { if (h == 0) cur.v[k].x = Xo[k]; else cur.v[k].y = Xo[k]; }
-#pragma unroll
-          for (int k = 0; k < 6; ++k) { if (h == 0) cur.v[3 + k].x = So[k]; else cur.v[3 + k].y = So[k]; }
-        }
-        __builtin_amdgcn_sched_barrier(0);                 // one landmark at a time, as in landmarks_fuse_kernel
-      }
-      if (chi2) reinterpret_cast<double2*>(chi2)[p] = make_double2(s[0], s[1]);
-      if (APPLY && (fused[0] || fused[1])) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) lr_plane(base, elems, k)[p] = cur.v[k];
-        uint2* cp = reinterpret_cast<uint2*>(lr_counts(base, elems)) + p;
-        uint2 c = *cp;
-        c.x += fused[0] ? 1u : 0u;
-        c.y += fused[1] ? 1u : 0u;
-        *cp = c;
-      }
-    }
-  }
-  cc.flush(counters);
+  constexpr bool NOISE = true;
+#define SBA_LANDMARK_PASS_ONE(X, Sg, y, nz, Xo, So, chi2) landmark_register_one(P, X, Sg, y, nz, Xo, So, chi2)
+#include "sba_landmarks_pass.inc"
+#undef SBA_LANDMARK_PASS_ONE
 }
 
 const void* register_kernel_of(int which, bool indexed, bool apply) {
