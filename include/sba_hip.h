@@ -712,7 +712,8 @@ int sba_landmarks_gather_device(sba_landmarks* h, const int64_t* idx /* [m], hos
  * (d* <= 0 at the freeze or at the solution), GATED (chi2 > chi2_gate AT THE SOLUTION), FUSED.  Observations skipped or behind at
  * the freeze take no part in the solve.  GATED observations DID take part in it, and so did those found behind only at the
  * solution: the solve has no robust loss, and a caller who wants them out registers again without them (chi2_out and a dry run
- * tell which).  Only a fused landmark is rewritten, and its count incremented.
+ * tell which).  Only a fused landmark is rewritten, and its count incremented.  sba_landmarks_register_robust (below) is the
+ * same solve under a Huber loss, for frames that carry wrong matches.
  * Refusals, all before the first device call with nothing written and the handle usable: a NULL argument, a bad bearing_sigma,
  * chi2_gate, idx or m: SBA_ERR_INVALID_ARG; lm.huber_delta != 0: SBA_ERR_UNSUPPORTED; a non-finite pose: SBA_ERR_NUMERIC; a
  * poisoned handle: SBA_ERR_HIP.  After the freeze, with the map untouched: fewer than 3 observations that take part, a failed
@@ -752,6 +753,62 @@ int sba_landmarks_eval_register(sba_landmarks* h, const int64_t* idx /* [m] or N
 int sba_landmarks_register(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */, size_t m,
                            const double rot0[3], const double tran0[3], const sba_landmark_register_options* opt,
                            sba_landmark_register_result* res, double* chi2_out /* [m] or NULL */);
+
+/* ---- the landmark map: the joint registration under a robust loss ------------------------------------------------------ */
+/* THE OBJECTIVE.  With f_j the block of landmark j in sba_landmarks_register's F (its bearing term plus its prior term), the loss
+ * sits on every block, as Ceres applies a loss to a residual block:
+ *     F_rho = sum_j rho( min_X f_j(X, pose) )
+ * rho is monotone, so the minimisation over X_j passes through it: eliminating the landmark is still exact, Xh_j is unchanged,
+ * and F_rho(pose) = sum_j rho(chi2_j) with chi2_j = u . u as above remains.  rho is the project's Huber, rho(s) = s for
+ * s <= delta^2 and 2 delta sqrt(s) - delta^2 beyond, w = rho'(s), delta = lm.huber_delta on the whitened, dimensionless |u|.
+ *     H = sum w_j J_w^T J_w  (Gauss-Newton, no second-order loss term),  g = sum w_j J_w^T u  (the exact gradient of 1/2 F_rho),
+ *     cost = 1/2 sum rho(chi2_j),  n_outlier = the observations that entered the sums with chi2_j > delta^2
+ * THE WRITE-BACK is sba_landmarks_register's with Sigma_c = H_rho^-1 at the solution and classes by chi2_gate, and chi2_gate >
+ * delta^2 IS REFUSED (+inf counts as larger): an observation the loss downweights has w < 1, the conditional covariance of its
+ * block would be Sigma_cond / w, and fusing it would inflate the landmark.  With chi2_gate <= delta^2 every fused observation had
+ * weight exactly 1, so its posterior X+ = Xh, Sigma+ = Sigma_cond + G Sigma_c G^T is the weighted problem's own, and every
+ * downweighted observation is GATED: its landmark stays untouched, byte for byte.
+ * opt: sba_landmark_register_options with lm.huber_delta finite and > 0.  The records are the non-robust ones followed by
+ * n_outlier.  The _device twins take `bearings` as a DEVICE pointer to 3 m doubles in the same row layout (8-byte aligned), on
+ * the handle's device and complete on its stream, and sba_landmarks_register_robust_device writes chi2_out to DEVICE memory (m
+ * doubles, or NULL).  The kernels read the caller's bearings in place; only the dense form over an odd n, or from a pointer that
+ * is not 16-byte aligned, is first copied device to device, because its 16-byte vector loads would otherwise end behind the
+ * caller's array.  idx stays on the host: it is checked there before the first device call.
+ * Refusals, all before the first device call with nothing written and the handle usable: everything sba_landmarks_register
+ * refuses, with the same codes, the loss excepted; lm.huber_delta NaN, infinite or <= 0, chi2_gate > delta^2, a misaligned
+ * device pointer: SBA_ERR_INVALID_ARG.  After the freeze the same SBA_ERR_NUMERIC cases as sba_landmarks_register.            */
+typedef struct sba_landmark_register_robust_result {
+  double rot[3], tran[3];      /* the solved pose */
+  double cov[36];              /* Sigma_c = H_rho^-1, row-major over [rot | tran] */
+  sba_lm_summary summary;
+  long long n_obs;             /* = n_skipped + n_behind + n_gated + n_fused */
+  long long n_skipped, n_behind, n_gated, n_fused;
+  long long n_used;            /* observations that entered the sums at the solution */
+  long long n_outlier;         /* of which: chi2 > delta^2 at the solution */
+} sba_landmark_register_robust_result;
+typedef struct sba_landmark_register_robust_eval {
+  double H[36];                /* row-major symmetric 6 x 6 over [rot | tran] */
+  double g[6];
+  double cost;
+  long long n_used;            /* observations that entered the sums */
+  long long n_behind;          /* of which: d* <= 0 at the evaluation pose */
+  long long n_outlier;         /* of which: chi2 > delta^2 */
+} sba_landmark_register_robust_eval;
+int sba_landmarks_eval_register_robust(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */,
+                                       size_t m, const double rot[3], const double tran[3], const double rot_ref[3],
+                                       const double tran_ref[3], const sba_landmark_register_options* opt,
+                                       sba_landmark_register_robust_eval* eval);
+int sba_landmarks_register_robust(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */,
+                                  size_t m, const double rot0[3], const double tran0[3], const sba_landmark_register_options* opt,
+                                  sba_landmark_register_robust_result* res, double* chi2_out /* [m] or NULL */);
+int sba_landmarks_eval_register_robust_device(sba_landmarks* h, const int64_t* idx /* [m], host, or NULL */,
+                                              const void* bearings_dev /* double[3 m], device */, size_t m, const double rot[3],
+                                              const double tran[3], const double rot_ref[3], const double tran_ref[3],
+                                              const sba_landmark_register_options* opt, sba_landmark_register_robust_eval* eval);
+int sba_landmarks_register_robust_device(sba_landmarks* h, const int64_t* idx /* [m], host, or NULL */,
+                                         const void* bearings_dev /* double[3 m], device */, size_t m, const double rot0[3],
+                                         const double tran0[3], const sba_landmark_register_options* opt,
+                                         sba_landmark_register_robust_result* res, void* chi2_out_dev /* double[m], device, or NULL */);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

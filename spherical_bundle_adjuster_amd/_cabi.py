@@ -145,7 +145,15 @@ class LandmarkRegisterEval(C.Structure):
                 ("n_behind", C.c_longlong)]
 
 
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
+class LandmarkRegisterRobustResult(C.Structure):
+    _fields_ = LandmarkRegisterResult._fields_ + [("n_outlier", C.c_longlong)]
+
+
+class LandmarkRegisterRobustEval(C.Structure):
+    _fields_ = LandmarkRegisterEval._fields_ + [("n_outlier", C.c_longlong)]
+
+
+ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -233,6 +241,14 @@ SIGNATURES = {
                                               C.POINTER(LandmarkRegisterOptions), C.POINTER(LandmarkRegisterEval)]),
     "sba_landmarks_register": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp, C.POINTER(LandmarkRegisterOptions),
                                          C.POINTER(LandmarkRegisterResult), _dp]),
+    "sba_landmarks_eval_register_robust": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp, _dp, _dp,
+                                                     C.POINTER(LandmarkRegisterOptions), C.POINTER(LandmarkRegisterRobustEval)]),
+    "sba_landmarks_register_robust": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp, C.POINTER(LandmarkRegisterOptions),
+                                                C.POINTER(LandmarkRegisterRobustResult), _dp]),
+    "sba_landmarks_eval_register_robust_device": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.c_size_t, _dp, _dp, _dp, _dp,
+                                                            C.POINTER(LandmarkRegisterOptions), C.POINTER(LandmarkRegisterRobustEval)]),
+    "sba_landmarks_register_robust_device": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.c_size_t, _dp, _dp,
+                                                       C.POINTER(LandmarkRegisterOptions), C.POINTER(LandmarkRegisterRobustResult), _vp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

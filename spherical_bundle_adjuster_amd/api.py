@@ -145,6 +145,20 @@ class LandmarkRegistration:
 
 
 @dataclass
+class LandmarkRobustRegisterEquations(LandmarkRegisterEquations):
+    """One evaluation of the robust joint registration (Landmarks.eval_register_robust): H = sum w J_w^T J_w, g = sum w J_w^T u,
+    cost = 1/2 sum rho(chi2) with the Huber loss on every landmark's chi2 and w = rho'."""
+    n_outlier: int         # of the used observations: chi2 > huber_delta^2
+
+
+@dataclass
+class LandmarkRobustRegistration(LandmarkRegistration):
+    """What one Landmarks.register_robust did: LandmarkRegistration under the Huber loss; cov = H_rho^-1.  With bearings on the
+    device and chi2 asked for, chi2 is what the caller passed as chi2_device (the address), not an array."""
+    n_outlier: int         # observations with chi2 > huber_delta^2 at the solution: all of them are gated
+
+
+@dataclass
 class LandmarkPrune:
     """What one Landmarks.prune did: every landmark falls into exactly one class, tested in this order, n_before = n_invalid +
     n_uncertain + n_unobserved + n_masked + n_kept.  invalid: a non-finite entry of X or Sigma or a negative variance; uncertain:
@@ -1145,6 +1159,75 @@ class Landmarks:
         return LandmarkRegistration(np.array(res.rot, dtype=np.float64), np.array(res.tran, dtype=np.float64),
                                     np.array(res.cov, dtype=np.float64).reshape(6, 6), _summary(res.summary), int(res.n_obs),
                                     int(res.n_skipped), int(res.n_behind), int(res.n_gated), int(res.n_fused), int(res.n_used), chi2)
+
+    def _robust_args(self, bearings, bearings_device, m, idx, huber_delta, bearing_sigma, chi2_gate, apply, options):
+        """(bearings pointer, m, idx array, options, the host bearings to keep alive) of the two robust methods."""
+        if (bearings is None) == (bearings_device is None):
+            raise ValueError("give either bearings or bearings_device")
+        ii = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        if bearings_device is None:
+            y = _f64(bearings).reshape(-1, 3)
+            m, ptr = y.shape[0], _dptr(y)
+        else:
+            if m is None:
+                if ii is None:
+                    m = self.size
+                else:
+                    m = ii.shape[0]
+            y, ptr = None, C.c_void_p(int(bearings_device))
+        if ii is not None and ii.shape[0] != m:
+            raise ValueError("one index per bearing")
+        opt = cabi.LandmarkRegisterOptions()
+        gate = float(huber_delta) ** 2 if chi2_gate is None else float(chi2_gate)
+        opt.bearing_sigma, opt.chi2_gate, opt.apply = float(bearing_sigma), gate, 1 if apply else 0
+        opt.lm = options if options is not None else default_lm_options()
+        opt.lm.huber_delta = float(huber_delta)
+        return ptr, int(m), ii, opt, y
+
+    def eval_register_robust(self, bearings, rot, tran, huber_delta: float, rot_ref=None, tran_ref=None, bearing_sigma: float = 0.0,
+                             idx=None, bearings_device=None, m: int | None = None) -> LandmarkRobustRegisterEquations:
+        """eval_register under the Huber loss on every landmark's chi2 (huber_delta > 0, in units of the whitened residual).
+        bearings_device: instead of `bearings` (then None), the address of m * 3 float64 on the handle's device, for example
+        ``tensor.data_ptr()``; m defaults to len(idx), or to the map's size in the dense form."""
+        ptr, m, ii, opt, keep = self._robust_args(bearings, bearings_device, m, idx, huber_delta, bearing_sigma, None, False, None)
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        rot_ref = rot if rot_ref is None else _f64(rot_ref, (3,))
+        tran_ref = tran if tran_ref is None else _f64(tran_ref, (3,))
+        ev = cabi.LandmarkRegisterRobustEval()
+        fn = self._lib.sba_landmarks_eval_register_robust if bearings_device is None else self._lib.sba_landmarks_eval_register_robust_device
+        cabi.check(self._lib, fn(self._h, None if ii is None else ii.ctypes.data_as(C.POINTER(C.c_int64)), ptr, m, _dptr(rot), _dptr(tran),
+                                 _dptr(rot_ref), _dptr(tran_ref), C.byref(opt), C.byref(ev)))
+        return LandmarkRobustRegisterEquations(np.array(ev.H, dtype=np.float64).reshape(6, 6), np.array(ev.g, dtype=np.float64), float(ev.cost),
+                                               int(ev.n_used), int(ev.n_behind), int(ev.n_outlier))
+
+    def register_robust(self, bearings, rot, tran, huber_delta: float, bearing_sigma: float = 0.0, chi2_gate: float | None = None, idx=None,
+                        apply: bool = True, options: cabi.LmOptions | None = None, return_chi2: bool = False, bearings_device=None,
+                        m: int | None = None, chi2_device=None) -> LandmarkRobustRegistration:
+        """`register` under the Huber loss on every landmark's chi2: wrong matches are downweighted in the solve and gated in
+        the write-back.  chi2_gate defaults to huber_delta^2, the largest value accepted: a downweighted observation must not
+        be fused (its conditional covariance would be inflated by 1 / w).  options: LM options whose huber_delta is replaced by
+        `huber_delta`.  bearings_device as for eval_register_robust; with it chi2 goes to chi2_device (the address of m float64
+        on the device, or None) instead of return_chi2's host array."""
+        ptr, m, ii, opt, keep = self._robust_args(bearings, bearings_device, m, idx, huber_delta, bearing_sigma, chi2_gate, apply, options)
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        res = cabi.LandmarkRegisterRobustResult()
+        ip = None if ii is None else ii.ctypes.data_as(C.POINTER(C.c_int64))
+        if bearings_device is None:
+            if chi2_device is not None:
+                raise ValueError("chi2_device goes with bearings_device")
+            chi2 = np.full(m, np.nan) if return_chi2 else None
+            cabi.check(self._lib, self._lib.sba_landmarks_register_robust(
+                self._h, ip, ptr, m, _dptr(rot), _dptr(tran), C.byref(opt), C.byref(res), None if chi2 is None else _dptr(chi2)))
+        else:
+            if return_chi2:
+                raise ValueError("with bearings_device chi2 is written to chi2_device")
+            chi2 = chi2_device
+            cabi.check(self._lib, self._lib.sba_landmarks_register_robust_device(
+                self._h, ip, ptr, m, _dptr(rot), _dptr(tran), C.byref(opt), C.byref(res), C.c_void_p(int(chi2_device) if chi2_device else 0)))
+        return LandmarkRobustRegistration(np.array(res.rot, dtype=np.float64), np.array(res.tran, dtype=np.float64),
+                                          np.array(res.cov, dtype=np.float64).reshape(6, 6), _summary(res.summary), int(res.n_obs),
+                                          int(res.n_skipped), int(res.n_behind), int(res.n_gated), int(res.n_fused), int(res.n_used), chi2,
+                                          int(res.n_outlier))
 
     # -- edits: the counts survive all of them -------------------------------------------------------
     def scores(self) -> np.ndarray:

@@ -518,6 +518,15 @@ hipError_t launch_landmarks_register_reduce(const LandmarkPlanes& pl, const Land
 hipError_t launch_landmarks_register_apply(const LandmarkPlanes& pl, const LandmarkRegisterParams& prm, const long long* idx, const double* bearings,
                                            const double* noise, double* chi2, unsigned long long* counters, bool apply, int grid, hipStream_t stream);
 
+// The robust joint registration's reduce pass (sba_landmarks_register_robust.hip; the objective, LandmarkRegisterRobust and the
+// per-observation code: sba_landmarks_register_robust.hpp): launch_landmarks_register_reduce's arguments and the loss, the
+// outlier count in slot SBA_RESECT_NOUT.  Its freeze and its write-back are the two launches above.
+struct LandmarkRegisterRobust;
+hipError_t landmarks_register_robust_blocks_per_cu(bool indexed, int* blocks);   // resident 256-thread blocks per CU
+hipError_t launch_landmarks_register_robust_reduce(const LandmarkPlanes& pl, const LandmarkRegisterParams& prm, const LandmarkRegisterRobust& loss,
+                                                   const long long* idx, const double* bearings, const double* noise, double* partials, int grid,
+                                                   double* out, hipStream_t stream);
+
 // Edits of the landmark map (sba_landmarks_edit.hip; the score, the classes of a prune and the checks: sba_landmarks_edit.hpp).
 // Scores: out [elems] doubles (device, 16-byte aligned).  Keep: one streaming pass that writes keep[ntiles * kCompactTile] bytes
 // (1 = kept, 0 beyond n) and adds the LANDMARK_PRUNE_CLASSES class counts to `counters` (zeroed by the launcher):

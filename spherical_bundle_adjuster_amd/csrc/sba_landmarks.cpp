@@ -4,7 +4,8 @@
 // index checks: sba_landmarks.hpp.  Below them the edits of the map -- scores, prune, append, gather -- with their kernels in
 // sba_landmarks_edit.hip and their checks in sba_landmarks_edit.hpp, and at the end the joint registration of a frame -- its pose
 // and its landmarks solved together -- with its kernels in sba_landmarks_register.hip and its per-observation code in
-// sba_landmarks_register.hpp.  Every wait is the bounded stream_wait; a handle whose wait gave up is poisoned.
+// sba_landmarks_register.hpp, and last its robust form (sba_landmarks_register_robust.hpp, sba_landmarks_register_robust.hip).
+// Every wait is the bounded stream_wait; a handle whose wait gave up is poisoned.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -18,6 +19,7 @@
 #include "sba_landmarks.hpp"
 #include "sba_landmarks_edit.hpp"
 #include "sba_landmarks_register.hpp"
+#include "sba_landmarks_register_robust.hpp"
 #include "sba_lm.hpp"
 
 struct sba_landmarks {
@@ -47,6 +49,7 @@ struct sba_landmarks {
   void* reg = nullptr;
   size_t reg_bytes = 0;
   int occ_reg[sba::LANDMARK_REGISTER_KERNELS][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};   // per [kernel][indexed][apply]
+  int occ_reg_robust[2] = {0, 0};          // ... of landmarks_register_robust_reduce_kernel per [indexed]
 };
 
 namespace {
@@ -85,6 +88,9 @@ int edit_occ(sba_landmarks* h, int which, int* occ) {
 int register_occ(sba_landmarks* h, int which, bool indexed, bool apply, int* occ) {
   return cached_occ(&h->occ_reg[which][indexed ? 1 : 0][apply ? 1 : 0],
                     [&](int* o) { return sba::landmarks_register_blocks_per_cu(which, indexed, apply, o); }, occ);
+}
+int register_robust_occ(sba_landmarks* h, bool indexed, int* occ) {
+  return cached_occ(&h->occ_reg_robust[indexed ? 1 : 0], [&](int* o) { return sba::landmarks_register_robust_blocks_per_cu(indexed, o); }, occ);
 }
 
 // Grow-only device scratch of a handle: at least `need` bytes behind *ptr afterwards.  What it held is lost when it grows.
@@ -709,6 +715,227 @@ int sba_landmarks_register(sba_landmarks* h, const int64_t* idx, const double* b
   sum.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
   res->summary = sum;
   return SBA_OK;
+}
+
+}  // extern "C"
+
+// ---- the robust joint registration: the Huber loss on every landmark's block (sba_landmarks_register_robust.hpp) --------------------
+namespace {
+
+// The refusals of the four robust entry points, all before the first device call: register_check's with the same codes, the
+// loss excepted, then the loss and the gate against delta^2.  on_device: bearings (and chi2_out) are device pointers to doubles.
+int robust_check(sba_landmarks* h, const int64_t* idx, const void* bearings, size_t m, const double* rot, const double* tran, const double* rot_ref,
+                 const double* tran_ref, const sba_landmark_register_options* opt, const void* out, bool on_device, const void* chi2_out) {
+  if (!h || !rot || !tran || !rot_ref || !tran_ref || !opt || !out || (m > 0 && !bearings)) return sba::set_error(SBA_ERR_INVALID_ARG, "null argument");
+  SBA_REFUSE_POISONED(h);
+  if (const char* why = sba::resect_weight_check_sigma(opt->bearing_sigma)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
+  if (const char* why = sba::landmark_check_gate(opt->chi2_gate)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
+  if (const char* why = sba::landmark_check_index(idx, m, h->n)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (m = %zu, n = %zu)", why, m, h->n);
+  if (const char* why = sba::landmark_register_check_robust(opt->lm.huber_delta, opt->chi2_gate)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
+  if (on_device && ((reinterpret_cast<uintptr_t>(bearings) | reinterpret_cast<uintptr_t>(chi2_out)) & 7u) != 0)
+    return sba::set_error(SBA_ERR_INVALID_ARG, "device bearings and chi2_out must be 8-byte aligned");
+  if (!finite3(rot) || !finite3(tran) || !finite3(rot_ref) || !finite3(tran_ref)) return sba::set_error(SBA_ERR_NUMERIC, "non-finite rot/tran");
+  return SBA_OK;
+}
+
+// Whether the dense form's 16-byte vector accesses stay inside a caller's device array of m rows: an even m (no padding row)
+// and a 16-byte aligned start.  The indexed form reads and writes single doubles of rows < m and always may.
+bool dense_vectors_fit(const void* ptr, size_t m) { return m % 2 == 0 && (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+
+// register_freeze for the robust pass: the grid of the reduce pass follows landmarks_register_robust_reduce_kernel's two
+// occupancies, and bearings may live on the device.  Device bearings are NOT copied: w->obs.bearings becomes the caller's pointer,
+// which every kernel takes as an argument of its own.  The one exception is the dense form over an odd n or from a start that
+// is not 16-byte aligned: its lanes load whole 16-byte vectors of two rows, the last of which would end 24 bytes behind the
+// caller's array, so those rows go device-to-device into the scratch with its zeroed padding row.
+int robust_freeze(sba_landmarks* h, const int64_t* idx, const double* bearings, bool on_device, size_t m, const double rot_ref[3],
+                  const double tran_ref[3], double bearing_sigma, RegisterWork* w) {
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  const size_t elems = h->elems;
+  int rc = obs_scratch(h, true, &w->obs);
+  if (rc) return rc;
+  w->indexed = idx != nullptr;
+  w->m = m;
+  w->bearing_sigma = bearing_sigma;
+  const size_t items = w->indexed ? m : elems / 2;
+  int occ = 1, occ_other = 1;
+  rc = register_occ(h, sba::LANDMARK_REGISTER_FREEZE, w->indexed, false, &occ);
+  if (rc) return rc;
+  w->grid_freeze = grid_for(h, items, occ);
+  rc = register_robust_occ(h, w->indexed, &occ);
+  if (rc) return rc;
+  rc = register_robust_occ(h, !w->indexed, &occ_other);
+  if (rc) return rc;
+  w->grid_reduce = grid_for(h, w->indexed ? (m + 1) / 2 : elems / 2, std::min(occ, occ_other));
+  rc = grow_scratch(&h->reg, &h->reg_bytes, kCounterBytes + (static_cast<size_t>(w->grid_reduce) + 1) * sba::JOINT_ROW * sizeof(double));
+  if (rc) return rc;
+  w->freeze_counters = static_cast<unsigned long long*>(h->reg);
+  w->row_dev = reinterpret_cast<double*>(w->freeze_counters + sba::LANDMARK_CLASSES);
+  w->partials = w->row_dev + sba::JOINT_ROW;
+  if (!on_device) {
+    rc = upload_observations(h, w->obs, idx, bearings, m);
+    if (rc) return rc;
+  } else if (w->indexed) {
+    SBA_TRY_HIP(hipMemcpyAsync(w->obs.idx, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    w->obs.bearings = const_cast<double*>(bearings);
+  } else if (dense_vectors_fit(bearings, m)) {
+    w->obs.bearings = const_cast<double*>(bearings);
+  } else {
+    SBA_TRY_HIP(hipMemcpyAsync(w->obs.bearings, bearings, 3 * m * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (elems > m) SBA_TRY_HIP(hipMemsetAsync(w->obs.bearings + 3 * m, 0, 3 * (elems - m) * sizeof(double), h->stream));
+  }
+  sba::LandmarkRegisterParams prm;
+  sba::landmark_register_fill(h->n, m, rot_ref, tran_ref, nullptr, bearing_sigma, INFINITY, &prm);
+  SBA_TRY_HIP(sba::launch_landmarks_register_freeze(planes_of(h), prm, w->indexed ? w->obs.idx : nullptr, w->obs.bearings, w->obs.noise,
+                                                    w->freeze_counters, w->grid_freeze, h->stream));
+  unsigned long long host_counts[sba::LANDMARK_CLASSES] = {0, 0, 0, 0};
+  SBA_TRY_HIP(hipMemcpyAsync(host_counts, w->freeze_counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "robust landmark registration freeze", &h->poisoned);
+  if (rc) return rc;
+  for (int k = 0; k < sba::LANDMARK_CLASSES; ++k) w->freeze_counts[k] = static_cast<long long>(host_counts[k]);
+  return SBA_OK;
+}
+
+int robust_reduce_pass(sba_landmarks* h, const RegisterWork& w, const sba::LandmarkRegisterRobust& loss, const double rot[3], const double tran[3],
+                       double* row) {
+  sba::LandmarkRegisterParams prm;
+  sba::landmark_register_fill(h->n, w.m, rot, tran, nullptr, w.bearing_sigma, INFINITY, &prm);
+  SBA_TRY_HIP(sba::launch_landmarks_register_robust_reduce(planes_of(h), prm, loss, w.indexed ? w.obs.idx : nullptr, w.obs.bearings, w.obs.noise,
+                                                           w.partials, w.grid_reduce, w.row_dev, h->stream));
+  SBA_TRY_HIP(hipMemcpyAsync(row, w.row_dev, SBA_RESECT_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return sba::stream_wait(h->stream, "robust landmark registration reduce pass", &h->poisoned);
+}
+
+int eval_register_robust_common(sba_landmarks* h, const int64_t* idx, const double* bearings, bool on_device, size_t m, const double rot[3],
+                                const double tran[3], const double rot_ref[3], const double tran_ref[3], const sba_landmark_register_options* opt,
+                                sba_landmark_register_robust_eval* eval) {
+  int rc = robust_check(h, idx, bearings, m, rot, tran, rot_ref, tran_ref, opt, eval, on_device, nullptr);
+  if (rc) return rc;
+  *eval = sba_landmark_register_robust_eval{};
+  if (h->n == 0 || m == 0) return SBA_OK;
+  RegisterWork w;
+  rc = robust_freeze(h, idx, bearings, on_device, m, rot_ref, tran_ref, opt->bearing_sigma, &w);
+  if (rc) return rc;
+  sba::LandmarkRegisterRobust loss;
+  sba::landmark_register_robust_fill(opt->lm.huber_delta, &loss);
+  double row[sba::JOINT_ROW] = {0};
+  rc = robust_reduce_pass(h, w, loss, rot, tran, row);
+  if (rc) return rc;
+  if (!sba::resect_row_finite(row)) return sba::set_error(SBA_ERR_NUMERIC, "non-finite registration sums");
+  sba_normal_eq ne;
+  double n_behind = 0.0;
+  sba::resect_expand_row(row, &ne, &n_behind);
+  std::memcpy(eval->H, ne.H, sizeof(ne.H));
+  std::memcpy(eval->g, ne.g, sizeof(ne.g));
+  eval->cost = ne.cost;
+  eval->n_used = static_cast<long long>(ne.sum_w);
+  eval->n_behind = static_cast<long long>(n_behind);
+  eval->n_outlier = static_cast<long long>(ne.n_outlier);
+  return SBA_OK;
+}
+
+int register_robust_common(sba_landmarks* h, const int64_t* idx, const double* bearings, bool on_device, size_t m, const double rot0[3],
+                           const double tran0[3], const sba_landmark_register_options* opt, sba_landmark_register_robust_result* res,
+                           double* chi2_out) {
+  int rc = robust_check(h, idx, bearings, m, rot0, tran0, rot0, tran0, opt, res, on_device, chi2_out);
+  if (rc) return rc;
+  *res = sba_landmark_register_robust_result{};
+  for (int a = 0; a < 3; ++a) { res->rot[a] = rot0[a]; res->tran[a] = tran0[a]; }
+  if (h->n == 0 || m == 0) return SBA_OK;
+  const auto t_start = std::chrono::steady_clock::now();
+  RegisterWork w;
+  rc = robust_freeze(h, idx, bearings, on_device, m, rot0, tran0, opt->bearing_sigma, &w);
+  if (rc) return rc;
+  if (w.freeze_counts[sba::LANDMARK_LIVE] < 3)
+    return sba::set_error(SBA_ERR_NUMERIC, "pose not determined: %lld observations take part after the freeze (%lld skipped, %lld behind), 3 are needed",
+                          w.freeze_counts[sba::LANDMARK_LIVE], w.freeze_counts[sba::LANDMARK_SKIPPED], w.freeze_counts[sba::LANDMARK_BEHIND]);
+  sba::LandmarkRegisterRobust loss;
+  sba::landmark_register_robust_fill(opt->lm.huber_delta, &loss);
+  struct Visit { double rot[3], tran[3], H[36], n_used, n_outlier; };
+  std::vector<Visit> visits;
+  double seconds_eval = 0.0;
+  int eval_rc = SBA_OK;
+  auto evaluate = [&](const double r[3], const double t[3], sba_normal_eq* ne) -> bool {
+    const auto t0 = std::chrono::steady_clock::now();
+    double row[sba::JOINT_ROW] = {0};
+    eval_rc = robust_reduce_pass(h, w, loss, r, t, row);
+    seconds_eval += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (eval_rc) return false;
+    if (!sba::resect_row_finite(row)) return false;
+    sba::resect_expand_row(row, ne, nullptr);
+    Visit v;
+    for (int a = 0; a < 3; ++a) { v.rot[a] = r[a]; v.tran[a] = t[a]; }
+    std::memcpy(v.H, ne->H, sizeof(v.H));
+    v.n_used = ne->sum_w;
+    v.n_outlier = ne->n_outlier;
+    visits.push_back(v);
+    return true;
+  };
+  double r[3] = {rot0[0], rot0[1], rot0[2]}, t[3] = {tran0[0], tran0[1], tran0[2]};
+  sba_lm_summary sum;
+  std::memset(&sum, 0, sizeof(sum));
+  const int status = sba::lm_solve(SBA_MODE_RT, r, t, opt->lm, evaluate, &sum);
+  if (eval_rc) return eval_rc;
+  sum.seconds_eval = seconds_eval;
+  if (status != SBA_OK) return sba::set_error(status, "robust joint registration solve failed: non-finite sums or 5 consecutive invalid steps");
+  const Visit* at = nullptr;
+  for (size_t k = visits.size(); k-- > 0;)
+    if (std::memcmp(visits[k].rot, r, sizeof(r)) == 0 && std::memcmp(visits[k].tran, t, sizeof(t)) == 0) { at = &visits[k]; break; }
+  double cov[36];
+  if (!at || !sba::resect_cov_inverse(at->H, cov))
+    return sba::set_error(SBA_ERR_NUMERIC, "pose not determined: the reduced normal matrix is not positive definite at the solution");
+  // the write-back at the solution: sba_landmarks_register's, with Sigma_c = H_rho^-1
+  const bool apply = opt->apply != 0;
+  int occ = 1;
+  rc = register_occ(h, sba::LANDMARK_REGISTER_APPLY, w.indexed, apply, &occ);
+  if (rc) return rc;
+  // chi2 on the device goes straight to the caller where the pass's stores fit (dense_vectors_fit), else through the scratch
+  const bool chi2_direct = on_device && chi2_out && (w.indexed || dense_vectors_fit(chi2_out, m));
+  double* chi2_dev = !chi2_out ? nullptr : (chi2_direct ? chi2_out : w.obs.chi2);
+  sba::LandmarkRegisterParams prm;
+  sba::landmark_register_fill(h->n, m, r, t, cov, opt->bearing_sigma, opt->chi2_gate, &prm);
+  SBA_TRY_HIP(sba::launch_landmarks_register_apply(planes_of(h), prm, w.indexed ? w.obs.idx : nullptr, w.obs.bearings, w.obs.noise, chi2_dev,
+                                                   w.obs.counters, apply, grid_for(h, w.indexed ? m : h->elems / 2, occ), h->stream));
+  unsigned long long host_counts[sba::LANDMARK_CLASSES] = {0, 0, 0, 0};
+  SBA_TRY_HIP(hipMemcpyAsync(host_counts, w.obs.counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
+  if (chi2_out && !chi2_direct)
+    SBA_TRY_HIP(hipMemcpyAsync(chi2_out, w.obs.chi2, m * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "robust landmark registration write-back", &h->poisoned);
+  if (rc) return rc;
+  for (int a = 0; a < 3; ++a) { res->rot[a] = r[a]; res->tran[a] = t[a]; }
+  std::memcpy(res->cov, cov, sizeof(cov));
+  counts_to_result(host_counts, res);
+  res->n_used = static_cast<long long>(at->n_used);
+  res->n_outlier = static_cast<long long>(at->n_outlier);
+  sum.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+  res->summary = sum;
+  return SBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sba_landmarks_eval_register_robust(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double rot[3],
+                                       const double tran[3], const double rot_ref[3], const double tran_ref[3],
+                                       const sba_landmark_register_options* opt, sba_landmark_register_robust_eval* eval) {
+  return eval_register_robust_common(h, idx, bearings, false, m, rot, tran, rot_ref, tran_ref, opt, eval);
+}
+
+int sba_landmarks_register_robust(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double rot0[3], const double tran0[3],
+                                  const sba_landmark_register_options* opt, sba_landmark_register_robust_result* res, double* chi2_out) {
+  return register_robust_common(h, idx, bearings, false, m, rot0, tran0, opt, res, chi2_out);
+}
+
+int sba_landmarks_eval_register_robust_device(sba_landmarks* h, const int64_t* idx, const void* bearings_dev, size_t m, const double rot[3],
+                                              const double tran[3], const double rot_ref[3], const double tran_ref[3],
+                                              const sba_landmark_register_options* opt, sba_landmark_register_robust_eval* eval) {
+  return eval_register_robust_common(h, idx, static_cast<const double*>(bearings_dev), true, m, rot, tran, rot_ref, tran_ref, opt, eval);
+}
+
+int sba_landmarks_register_robust_device(sba_landmarks* h, const int64_t* idx, const void* bearings_dev, size_t m, const double rot0[3],
+                                         const double tran0[3], const sba_landmark_register_options* opt, sba_landmark_register_robust_result* res,
+                                         void* chi2_out_dev) {
+  return register_robust_common(h, idx, static_cast<const double*>(bearings_dev), true, m, rot0, tran0, opt, res, static_cast<double*>(chi2_out_dev));
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 """Workload for tools/profile_landmark_register.sh: the joint registration of a frame against the landmark map at 10^7 landmarks,
 dense, next to the d-only stage's pass and the fusion's dry run as the yardsticks of the same run.
 
-    python tools/landmark_register_workload.py [n] [calls]
+    python tools/landmark_register_workload.py [n] [calls] [--robust] [--device-bearings]
 
 In ONE process (one box: boxes differ by ~6 %), on the scene of tools/landmark_fusion_workload.py without its wrong matches (landmarks
 d1 * x1 drawn from a seeded covariance per landmark; bearings x2), the start 2e-3 rad and 1e-2 units off the true pose:
@@ -18,7 +18,13 @@ d1 * x1 drawn from a seeded covariance per landmark; bearings x2), the start 2e-
   * one registration with apply = True                              -> landmarks_register_apply_kernel<false, true>
 Every registration and every fusion uploads its 24 n bytes of bearings from the host first, and so does the chain (once, for the
 Problem): the host-side wall times hold those copies, the kernel trace does not.  Prints one JSON line with host-side wall times;
-the kernel times come from the rocprofv3 kernel trace."""
+the kernel times come from the rocprofv3 kernel trace.
+
+--robust (tools/profile_landmark_register_robust.sh): the scene WITH its wrong matches (full_rt's 5 % of bearings drawn anew), on
+which the same process runs the d-only stage, one non-robust evaluation (landmarks_register_reduce_kernel<false>: the yardsticks),
+then `calls` register_robust dry runs with host bearings, 3 indexed ones and one with apply = True
+(landmarks_register_robust_reduce_kernel<false> / <true>), Huber delta 3, gate delta^2.  --device-bearings adds the same dry runs
+with the bearings in device memory (bearings_device): the wall time without the 24 n byte upload."""
 import json
 import sys
 import time
@@ -39,10 +45,65 @@ def timed(calls, f):
     return 1e3 * (time.perf_counter() - t0) / calls, r
 
 
+def robust_main(n, calls, device_bearings):
+    import torch
+    delta = 3.0
+    out = {"n": n, "calls": calls, "robust": True, "huber_delta": delta}
+    c = synthetic.full_rt(n, seed=synthetic.BASE_SEED + 5)                               # with its wrong matches
+    rot, tran = c.rot_true, c.tran_true
+    truth = c.x1 * c.d12[:, :1]
+    cov, draw = covariances(truth, synthetic.BASE_SEED + 6)
+    X = truth + draw
+    rng = np.random.default_rng(synthetic.BASE_SEED + 7)
+    unit = lambda v: v / np.linalg.norm(v)
+    rot0, tran0 = rot + 2e-3 * unit(rng.standard_normal(3)), tran + 1e-2 * unit(rng.standard_normal(3))
+    with api.Problem(0) as p:
+        p.upload(c.x1, c.x2, np.full((n, 2), 5.0))
+        _, sd = p.solve_depths(rot, tran, options=api.default_lm_options(max_num_iterations=10))
+        out["depth_stage_us_per_pass"] = sd.seconds_total / max(sd.num_evaluations, 1) * 1e6
+    with api.Landmarks(0) as L:
+        out["set_ms"], _ = timed(1, lambda: L.set(X, cov))
+        L.eval_register(c.x2, rot0, tran0, bearing_sigma=1e-3)                           # the non-robust reduce pass: the yardstick
+        out["eval_register_host_ms"], _ = timed(calls, lambda: L.eval_register(c.x2, rot0, tran0, bearing_sigma=1e-3))
+        L.eval_register_robust(c.x2, rot0, tran0, delta, bearing_sigma=1e-3)
+        out["eval_register_robust_host_ms"], e = timed(calls, lambda: L.eval_register_robust(c.x2, rot0, tran0, delta, bearing_sigma=1e-3))
+        out["eval"] = {"n_used": e.n_used, "n_outlier": e.n_outlier}
+        reg = lambda **kw: L.register_robust(c.x2, rot0, tran0, delta, 1e-3, **kw)
+        reg(apply=False)                                                                 # first call: occupancy queries, scratch
+        out["register_robust_dry_host_ms"], f = timed(calls, lambda: reg(apply=False))
+        out["register"] = {"termination": f.summary.termination, "iterations": f.summary.num_iterations, "evaluations": f.summary.num_evaluations,
+                           "seconds_eval": f.summary.seconds_eval, "n_fused": f.n_fused, "n_gated": f.n_gated, "n_used": f.n_used,
+                           "n_outlier": f.n_outlier, "pose_error": [float(np.abs(f.rot - rot).max()), float(np.abs(f.tran - tran).max())]}
+        idx = np.arange(0, n, 2, dtype=np.int64)
+        y2 = np.ascontiguousarray(c.x2[idx])
+        out["register_robust_indexed_dry_host_ms"], h = timed(3, lambda: L.register_robust(y2, rot0, tran0, delta, 1e-3, idx=idx, apply=False))
+        out["indexed"] = {"m": int(len(idx)), "n_fused": h.n_fused, "evaluations": h.summary.num_evaluations}
+        if device_bearings:
+            ty = torch.from_numpy(np.ascontiguousarray(c.x2)).to(torch.device("cuda", 0))
+            torch.cuda.synchronize()
+            dreg = lambda: L.register_robust(None, rot0, tran0, delta, 1e-3, apply=False, bearings_device=ty.data_ptr(), m=n)
+            g = dreg()
+            out["register_robust_device_dry_host_ms"], g = timed(calls, dreg)
+            out["device"] = {"evaluations": g.summary.num_evaluations, "n_fused": g.n_fused,
+                             "same_pose": bool(np.array_equal(g.rot, f.rot) and np.array_equal(g.tran, f.tran))}
+        out["register_robust_apply_host_ms"], a = timed(1, lambda: reg(apply=True))
+        Xg, Cg = L.get()
+        out["result"] = {"finite": bool(np.isfinite(Xg).all() and np.isfinite(Cg).all()), "max_count": int(L.counts().max()),
+                         "n_fused": a.n_fused, "n_outlier": a.n_outlier, "rms_before": float(np.sqrt(np.mean(np.sum(draw ** 2, axis=1)))),
+                         "rms_after": float(np.sqrt(np.mean(np.sum((Xg - truth) ** 2, axis=1))))}
+    print(json.dumps(out))
+
+
 def main():
     import torch
+    flags = [a for a in sys.argv[1:] if a.startswith("--")]
+    sys.argv = sys.argv[:1] + [a for a in sys.argv[1:] if not a.startswith("--")]
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
     calls = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    if set(flags) - {"--robust", "--device-bearings"}:
+        raise SystemExit(__doc__)
+    if "--robust" in flags or "--device-bearings" in flags:
+        return robust_main(n, calls, "--device-bearings" in flags)
     out = {"n": n, "calls": calls}
     c = synthetic.full_rt(n, seed=synthetic.BASE_SEED + 5, outlier_fraction=0.0)     # no wrong matches: the joint solve has no robust loss
     rot, tran = c.rot_true, c.tran_true
