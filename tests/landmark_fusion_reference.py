@@ -74,8 +74,9 @@ def _classify(bad, dstar, chi2, gate, Xp, Cp):
     return cls.astype(int)
 
 
-def fuse(X, cov6, y, rot, tran, bearing_sigma=0.0, gate=np.inf, pose_cov=None, dtype=LD):
-    """The reference: one bearing per landmark (rows correspond), basis-free, per observation in `dtype`."""
+def fuse(X, cov6, y, rot, tran, bearing_sigma=0.0, gate=np.inf, pose_cov=None, dtype=LD, projected=False):
+    """The reference: one bearing per landmark (rows correspond), basis-free, per observation in `dtype`.  projected: M as
+    Q (Q^T S Q)^-1 Q^T, which forms no S^-1 and so holds for a singular S (resection_weighted_reference.projected_weight)."""
     n = len(X)
     if n == 0:
         return _empty(dtype)
@@ -95,10 +96,13 @@ def fuse(X, cov6, y, rot, tran, bearing_sigma=0.0, gate=np.inf, pose_cov=None, d
         c22 = np.einsum("ia,iab,ib->i", q2, S, q2)
         bad |= ~((c11 > 0) & (c11 * c22 - c12 * c12 > 0))
         Ssafe = np.where(bad[:, None, None], np.eye(3, dtype=dtype)[None], S)
-        Si, _ = wr._adjugate_inverse(Ssafe)
         ysafe = np.where(bad[:, None], np.array([1, 0, 0], dtype=dtype)[None], y)
-        v = np.einsum("iab,ib->ia", Si, ysafe)
-        M = Si - v[:, :, None] * v[:, None, :] / np.sum(v * ysafe, axis=1)[:, None, None]
+        if projected:
+            M = wr.projected_weight(Ssafe, ysafe, dtype)
+        else:
+            Si, _ = wr._adjugate_inverse(Ssafe)
+            v = np.einsum("iab,ib->ia", Si, ysafe)
+            M = Si - v[:, :, None] * v[:, None, :] / np.sum(v * ysafe, axis=1)[:, None, None]
         G = Sg @ R.T[None]                                   # Sigma R^T
         GM = G @ M
         Cp = wr.rows_of(Sg - GM @ np.swapaxes(G, 1, 2))
@@ -150,7 +154,7 @@ def errors(got_X, got_cov, got_chi2, ref, prior_X, prior_cov):
     if f.any():
         nX = np.sqrt(np.sum(np.asarray(prior_X, dtype=LD)[f] ** 2, axis=1))
         ex = float((np.abs(np.asarray(got_X, dtype=LD)[f] - ref.X[f]).max(axis=1) / nX).max())
-        sc = np.abs(np.asarray(prior_cov, dtype=LD)[f]).max(axis=1)
+        sc = np.maximum(np.abs(np.asarray(prior_cov, dtype=LD)[f]).max(axis=1), LD(1e-300))      # Sigma = 0 stays 0: any error there is huge
         ec = float((np.abs(np.asarray(got_cov, dtype=LD)[f] - ref.cov[f]).max(axis=1) / sc).max())
     if live.any():
         rs = ref.chi2[live]

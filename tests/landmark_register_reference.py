@@ -51,16 +51,15 @@ class Point:
     W: np.ndarray | None   # (n, 2, 3), the basis form only
 
 
+PROJECTED = "projected"             # point(..., basis=PROJECTED): the reference formulation that forms no S^-1
+
+
 def _pd_across(S, y, dtype):
-    k = np.argmin(np.abs(y), axis=1)
-    q1 = np.cross(np.eye(3, dtype=dtype)[k], y)
-    q1 = q1 / np.sqrt(np.sum(q1 * q1, axis=1))[:, None]
-    q2 = np.cross(y, q1)
-    q2 = q2 / np.sqrt(np.sum(q2 * q2, axis=1))[:, None]
-    c11 = np.einsum("ia,iab,ib->i", q1, S, q1)
-    c12 = np.einsum("ia,iab,ib->i", q1, S, q2)
-    c22 = np.einsum("ia,iab,ib->i", q2, S, q2)
+    _, _, c11, c12, c22 = wr.across(S, y, dtype)
     return (c11 > 0) & (c11 * c22 - c12 * c12 > 0)
+
+
+projected_weight = wr.projected_weight
 
 
 def point(X, cov6, y, noise2, rot, tran, dtype=LD, basis=False):
@@ -71,7 +70,7 @@ def point(X, cov6, y, noise2, rot, tran, dtype=LD, basis=False):
         _, dstar, r, _, _ = rr.per_match(X, y, rot, tran, dtype)
         Sg = wr.full(cov6, dtype)
         S = R[None] @ Sg @ R.T[None] + np.asarray(noise2, dtype=dtype)[:, None, None] * np.eye(3, dtype=dtype)[None]
-        if basis:
+        if basis is True:
             b1, b2 = wr.basis(y)
             c11 = np.einsum("ia,iab,ib->i", b1, S, b1)
             c12 = np.einsum("ia,iab,ib->i", b1, S, b2)
@@ -91,9 +90,12 @@ def point(X, cov6, y, noise2, rot, tran, dtype=LD, basis=False):
         bad |= ~_pd_across(Ssafe, ysafe, dtype)
         Ssafe = np.where(bad[:, None, None], np.eye(3, dtype=dtype)[None], S)
         ysafe = np.where(bad[:, None], np.array([1, 0, 0], dtype=dtype)[None], y)
-        Si, _ = wr._adjugate_inverse(Ssafe)
-        v = np.einsum("iab,ib->ia", Si, ysafe)
-        M = Si - v[:, :, None] * v[:, None, :] / np.sum(v * ysafe, axis=1)[:, None, None]
+        if basis == PROJECTED:
+            M = projected_weight(Ssafe, ysafe, dtype)
+        else:
+            Si, _ = wr._adjugate_inverse(Ssafe)
+            v = np.einsum("iab,ib->ia", Si, ysafe)
+            M = Si - v[:, :, None] * v[:, None, :] / np.sum(v * ysafe, axis=1)[:, None, None]
         M = np.where(bad[:, None, None], dtype(0), M)
         r = np.where(bad[:, None], dtype(0), r)
     return Point(R, Sg, r, dstar, bad, M, None)
@@ -158,7 +160,7 @@ def evaluate(X, cov6, y, noise, rot, tran, dtype=LD, basis=False, raw=False):
         GM = pt.Sg @ pt.R.T[None] @ pt.M
         Xh = np.asarray(Xs, dtype=dtype) + np.einsum("iab,ib->ia", GM, pt.r)
         F = _jacobian(pt, Xh, rot, dtype)
-        if basis:
+        if basis is True:
             Jw = pt.W @ F
             u = np.einsum("ika,ia->ik", pt.W, pt.r)
             H, g, chi2 = np.einsum("ika,ikb->ab", Jw, Jw), np.einsum("ika,ik->a", Jw, u), np.sum(u * u, axis=1)
@@ -181,17 +183,17 @@ def eq_errors(got, ref):
 
 
 # ---- the solve: a Levenberg-Marquardt loop of its own --------------------------------------------------------------------------
-def solve(X, cov6, y, noise, rot, tran, dtype=LD, max_iterations=200, step_tol=1e-13):
+def solve(X, cov6, y, noise, rot, tran, dtype=LD, max_iterations=200, step_tol=1e-13, basis=False):
     """-> rot, tran (float64), the Equations there, iterations.  Damping lam diag(H): accepted steps divide lam by 3, rejected
     ones multiply it by 4; stops when an accepted step is below step_tol in every parameter."""
     p = np.concatenate([np.asarray(rot, dtype=np.float64), np.asarray(tran, dtype=np.float64)]).astype(dtype)
-    e = evaluate(X, cov6, y, noise, p[:3], p[3:], dtype, raw=True)
+    e = evaluate(X, cov6, y, noise, p[:3], p[3:], dtype, basis, raw=True)
     lam, it = dtype(1e-4), 0
     for it in range(1, max_iterations + 1):
         H, g = np.asarray(e.H, dtype=dtype), np.asarray(e.g, dtype=dtype)
         d = -(wr.inverse_ld(H + lam * np.diag(np.diag(H))) @ g)
         q = p + d
-        e2 = evaluate(X, cov6, y, noise, q[:3], q[3:], dtype, raw=True)
+        e2 = evaluate(X, cov6, y, noise, q[:3], q[3:], dtype, basis, raw=True)
         if e2.cost <= e.cost:
             p, e, lam = q, e2, lam / 3
             if np.abs(d).max() < step_tol:
@@ -208,12 +210,12 @@ def solve(X, cov6, y, noise, rot, tran, dtype=LD, max_iterations=200, step_tol=1
         if np.abs(d).max() < step_tol:
             break
         q = p + d
-        e2 = evaluate(X, cov6, y, noise, q[:3], q[3:], dtype, raw=True)
+        e2 = evaluate(X, cov6, y, noise, q[:3], q[3:], dtype, basis, raw=True)
         if not np.abs(e2.g).max() < np.abs(e.g).max():
             break
         p, e = q, e2
     p64 = p.astype(np.float64)
-    return p64[:3], p64[3:], evaluate(X, cov6, y, noise, p64[:3], p64[3:], dtype), it
+    return p64[:3], p64[3:], evaluate(X, cov6, y, noise, p64[:3], p64[3:], dtype, basis), it
 
 
 # ---- the posterior at a pose -----------------------------------------------------------------------------------------------------
@@ -253,7 +255,7 @@ def posterior(X, cov6, y, noise, rot, tran, gate=np.inf, dtype=LD, basis=False):
             GM = pt.Sg @ pt.R.T[None] @ pt.M
             Xh = np.asarray(Xs, dtype=dtype) + np.einsum("iab,ib->ia", GM, pt.r)
             F = _jacobian(pt, Xh, rot, dtype)
-            if basis:
+            if basis is True:
                 T = pt.Sg @ pt.R.T[None] @ np.swapaxes(pt.W, 1, 2)
                 cond = pt.Sg - T @ np.swapaxes(T, 1, 2)
                 G = T @ (pt.W @ F)
@@ -409,11 +411,12 @@ def solve_reference(n):
     return noise, cls, rot, tran, eq, it
 
 
-def qualify_posterior(X, cov, y, rot_ref, tran_ref, rot, tran, bs, gate=GATE):
+def qualify_posterior(X, cov, y, rot_ref, tran_ref, rot, tran, bs, gate=GATE, form=False):
     """The posterior at (rot, tran), noise frozen at (rot_ref, tran_ref): float64 in the product's formulation classifies as long
-    double does, no chi2 within MARGIN of the gate, no d* within MARGIN of 0 -> (ref, float64's (X+, Sigma+, chi2, Sigma_c) errors)."""
-    noise, cls = freeze(X, cov, y, rot_ref, tran_ref, bs)
-    ref = posterior(X, cov, y, noise, rot, tran, gate)
+    double does, no chi2 within MARGIN of the gate, no d* within MARGIN of 0 -> (ref, float64's (X+, Sigma+, chi2, Sigma_c) errors).
+    form: PROJECTED for the reference that holds for a singular S."""
+    noise, cls = freeze(X, cov, y, rot_ref, tran_ref, bs, basis=form)
+    ref = posterior(X, cov, y, noise, rot, tran, gate, basis=form)
     nb, cb = freeze(X, cov, y, rot_ref, tran_ref, bs, np.float64, basis=True)
     b = posterior(X, cov, y, nb, rot, tran, gate, np.float64, basis=True)
     assert np.array_equal(cls, cb) and np.array_equal(ref.cls, b.cls)

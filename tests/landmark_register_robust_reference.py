@@ -78,7 +78,7 @@ def _parts(Xs, Cs, ys, noise2, rot, tran, dtype, basis):
         GM = pt.Sg @ pt.R.T[None] @ pt.M
         Xh = np.asarray(Xs, dtype=dtype) + np.einsum("iab,ib->ia", GM, pt.r)
         F = lr._jacobian(pt, Xh, rot, dtype)
-        if basis:
+        if basis is True:
             u = np.einsum("ika,ia->ik", pt.W, pt.r)
             s = np.sum(u * u, axis=1)
         else:
@@ -86,13 +86,13 @@ def _parts(Xs, Cs, ys, noise2, rot, tran, dtype, basis):
     return pt, GM, Xh, F, s
 
 
-def chi2_at(X, cov6, y, noise, rot, tran, dtype=LD):
+def chi2_at(X, cov6, y, noise, rot, tran, dtype=LD, basis=False):
     """chi2 of every observation that takes part (NaN elsewhere), and the mask of those the sums use."""
     live = lr.live_of(noise)
     s_all, used = np.full(len(X), np.nan, dtype=dtype), np.zeros(len(X), dtype=bool)
     if live.any():
         Xs, Cs, ys = (np.asarray(a, dtype=np.float64)[live] for a in (X, np.asarray(cov6).reshape(-1, 6), y))
-        pt, _, _, _, s = _parts(Xs, Cs, ys, np.asarray(noise, dtype=dtype)[live], rot, tran, dtype, False)
+        pt, _, _, _, s = _parts(Xs, Cs, ys, np.asarray(noise, dtype=dtype)[live], rot, tran, dtype, basis)
         s_all[live], used[live] = s, ~pt.bad
     return s_all, used
 
@@ -108,7 +108,7 @@ def evaluate(X, cov6, y, noise, rot, tran, delta, dtype=LD, basis=False, raw=Fal
     w, rho, out = huber(s, delta, dtype)
     w, rho, out = np.where(used, w, dtype(0)), np.where(used, rho, dtype(0)), out & used
     with np.errstate(all="ignore"):
-        if basis:
+        if basis is True:
             Jw = pt.W @ F
             u = np.einsum("ika,ia->ik", pt.W, pt.r)
             H, g = np.einsum("i,ika,ikb->ab", w, Jw, Jw), np.einsum("i,ika,ik->a", w, Jw, u)
@@ -132,10 +132,10 @@ def chi2_margin(s, used, bound):
 
 
 # ---- the solve: landmark_register_reference's loop over the robust sums -----------------------------------------------------
-def solve(X, cov6, y, noise, rot, tran, delta, dtype=LD, max_iterations=200, step_tol=1e-13):
+def solve(X, cov6, y, noise, rot, tran, delta, dtype=LD, max_iterations=200, step_tol=1e-13, basis=False):
     """-> rot, tran (float64), the Equations there, iterations: damping lam diag(H), accepted steps divide lam by 3, rejected ones
     multiply it by 4, until an accepted step is below step_tol; then undamped steps while they shrink the (exact) gradient."""
-    ev = lambda q: evaluate(X, cov6, y, noise, q[:3], q[3:], delta, dtype, raw=True)
+    ev = lambda q: evaluate(X, cov6, y, noise, q[:3], q[3:], delta, dtype, basis, raw=True)
     p = np.concatenate([np.asarray(rot, dtype=np.float64), np.asarray(tran, dtype=np.float64)]).astype(dtype)
     e = ev(p)
     lam, it = dtype(1e-4), 0
@@ -159,7 +159,7 @@ def solve(X, cov6, y, noise, rot, tran, delta, dtype=LD, max_iterations=200, ste
             break
         p, e = p + d, e2
     p64 = p.astype(np.float64)
-    return p64[:3], p64[3:], evaluate(X, cov6, y, noise, p64[:3], p64[3:], delta, dtype), it
+    return p64[:3], p64[3:], evaluate(X, cov6, y, noise, p64[:3], p64[3:], delta, dtype, basis), it
 
 
 # ---- the posterior at a pose -----------------------------------------------------------------------------------------------------
@@ -182,7 +182,7 @@ def posterior(X, cov6, y, noise, rot, tran, delta, gate=GATE, dtype=LD, basis=Fa
         nz = np.asarray(noise, dtype=dtype)[rows]
         pt, GM, Xh, F, s = _parts(Xs, Cs, ys, np.abs(nz), rot, tran, dtype, basis)
         with np.errstate(all="ignore"):
-            if basis:
+            if basis is True:
                 T = pt.Sg @ pt.R.T[None] @ np.swapaxes(pt.W, 1, 2)
                 cond = pt.Sg - T @ np.swapaxes(T, 1, 2)
                 G = T @ (pt.W @ F)
@@ -291,11 +291,11 @@ def pose_distance2(rot, tran, s, H):
     return float(d @ np.asarray(H, dtype=LD) @ d)
 
 
-def qualify_posterior(X, cov, y, rot_ref, tran_ref, rot, tran, bs, delta=DELTA, gate=GATE):
+def qualify_posterior(X, cov, y, rot_ref, tran_ref, rot, tran, bs, delta=DELTA, gate=GATE, form=False):
     """The posterior at (rot, tran): float64 in the product's formulation classifies as long double does, no chi2 within MARGIN
     of the gate or of delta^2, no d* within MARGIN of 0 -> (ref, float64's (X+, Sigma+, chi2, Sigma_c) errors)."""
-    noise, cls = lr.freeze(X, cov, y, rot_ref, tran_ref, bs)
-    ref = posterior(X, cov, y, noise, rot, tran, delta, gate)
+    noise, cls = lr.freeze(X, cov, y, rot_ref, tran_ref, bs, basis=form)
+    ref = posterior(X, cov, y, noise, rot, tran, delta, gate, basis=form)
     nb, cb = lr.freeze(X, cov, y, rot_ref, tran_ref, bs, np.float64, basis=True)
     b = posterior(X, cov, y, nb, rot, tran, delta, gate, np.float64, basis=True)
     assert np.array_equal(cls, cb) and np.array_equal(ref.cls, b.cls)

@@ -91,6 +91,33 @@ def _adjugate_inverse(S):
     return A / det[:, None, None], det
 
 
+def across(S, y, dtype=LD):
+    """A unit pair q1, q2 across y and the entries of Q^T S Q.  q1 = e_k x y with k the first smallest |y_k|: the k of the product's
+    resect_weight_basis, restated here and normalised."""
+    k = np.argmin(np.abs(y), axis=1)
+    q1 = np.cross(np.eye(3, dtype=dtype)[k], y)
+    q1 = q1 / np.sqrt(np.sum(q1 * q1, axis=1))[:, None]
+    q2 = np.cross(y, q1)
+    q2 = q2 / np.sqrt(np.sum(q2 * q2, axis=1))[:, None]
+    c11 = np.einsum("ia,iab,ib->i", q1, S, q1)
+    c12 = np.einsum("ia,iab,ib->i", q1, S, q2)
+    c22 = np.einsum("ia,iab,ib->i", q2, S, q2)
+    return q1, q2, c11, c12, c22
+
+
+def projected_weight(S, y, dtype=LD):
+    """M = Q (Q^T S Q)^-1 Q^T of rows whose S is positive definite across y, through the Cholesky factor of the 2 x 2 block: no
+    S^-1, so S itself may be singular (a prior of rank <= 2 with no bearing noise).  Equal to S^-1 - S^-1 y y^T S^-1 / (y^T S^-1 y)
+    wherever that exists."""
+    q1, q2, c11, c12, c22 = across(S, y, dtype)
+    g11 = np.sqrt(c11)
+    g21 = c12 / g11
+    g22 = np.sqrt(c22 - g21 * g21)
+    w1 = q1 / g11[:, None]
+    w2 = (q2 - (g21 / g11)[:, None] * q1) / g22[:, None]
+    return w1[:, :, None] * w1[:, None, :] + w2[:, :, None] * w2[:, None, :]
+
+
 def frozen_cov(X, y, cov6, rot_w, tran_w, cov_scale, bearing_sigma, dtype=LD):
     """S_i (n, 3, 3) at the reference pose, and d_i* there."""
     X, y = np.asarray(X, dtype=dtype), np.asarray(y, dtype=dtype)

@@ -92,13 +92,13 @@ def test_evaluation_over_several_grid_stride_steps(monkeypatch, n):
 
 
 # ---- 2. the solve and 3. the posterior -------------------------------------------------------------------------------------------
-def _check_posterior(L, X0, C0, cnt0, y, idx, rot0, tran0, bs, f, gate=lr.GATE):
+def _check_posterior(L, X0, C0, cnt0, y, idx, rot0, tran0, bs, f, gate=lr.GATE, form=False):
     """The handle's state after `f` against a reference step from the state before it, AT THE DEVICE'S POSE (so the stopping point
     does not enter), with bounds of 8 times float64 numpy's own errors on this very case."""
     global _worst_post
     n = len(X0)
     rows = np.arange(n) if idx is None else idx
-    ref, errs = lr.qualify_posterior(X0[rows], C0[rows], y, rot0, tran0, f.rot, f.tran, bs, gate)
+    ref, errs = lr.qualify_posterior(X0[rows], C0[rows], y, rot0, tran0, f.rot, f.tran, bs, gate, form)
     assert _counts(f) == ref.counts(), (_counts(f), ref.counts())
     assert f.n_used == ref.eq.n_used
     X1, C1 = L.get()

@@ -6,15 +6,20 @@ within 1e-9 relative of delta^2): the vector-per-lane, wave and block edges, sev
 three rotations of tests/pose_edges.py (identity: the small-angle branch, one generic, one near pi), the noise frozen 1e-2 rad
 off the evaluation pose.  Counts are exact; H, g and the cost, and X+, Sigma+, chi2 and the pose covariance, are held to 8 times
 float64 numpy's own error on the same cases, measured in this run.  The solve against the reference's own
-minimiser; the posterior at the device's pose; the demonstration against the non-robust register; bytes across handles, forms,
-histories, grids and host / device bearings; refusals.  Every wait inside the library is its bounded stream wait."""
+minimiser; the posterior at the device's pose; planted rows of every class, at the given pose and solved; the demonstration
+against the non-robust register; bytes across handles, forms, histories, grids and host / device bearings, with guard cells around
+chi2 on the device; refusals; every entry point on a map that was pruned and appended to.  Every wait inside the library is its
+bounded stream wait."""
 from functools import lru_cache
 
 import numpy as np
 import pytest
 
+import landmark_edit_reference as le
+import landmark_fusion_reference as lf
 import landmark_register_reference as lr
 import landmark_register_robust_reference as rb
+import resection_reference as rr
 from spherical_bundle_adjuster_amd import _cabi as cabi
 from spherical_bundle_adjuster_amd import api
 
@@ -111,12 +116,12 @@ def test_evaluation_over_several_grid_stride_steps(monkeypatch, n):
 
 
 # ---- 2. the solve and the posterior ----------------------------------------------------------------------------------------------
-def _check_posterior(L, X0, C0, cnt0, y, idx, rot0, tran0, bs, f, gate=rb.GATE):
+def _check_posterior(L, X0, C0, cnt0, y, idx, rot0, tran0, bs, f, gate=rb.GATE, form=False):
     """The handle's state after `f` against a reference step from the state before it, AT THE DEVICE'S POSE, with bounds of 8 times
     float64 numpy's own errors on this very case; classes exact; every outlier's landmark untouched, byte for byte."""
     n = len(X0)
     rows = np.arange(n) if idx is None else idx
-    ref, errs = rb.qualify_posterior(X0[rows], C0[rows], y, rot0, tran0, f.rot, f.tran, bs, D, gate)
+    ref, errs = rb.qualify_posterior(X0[rows], C0[rows], y, rot0, tran0, f.rot, f.tran, bs, D, gate, form)
     assert _counts(f) == ref.counts(), (_counts(f), ref.counts())
     assert (f.n_used, f.n_outlier) == (ref.eq.n_used, ref.eq.n_outlier)
     X1, C1 = L.get()
@@ -125,7 +130,7 @@ def _check_posterior(L, X0, C0, cnt0, y, idx, rot0, tran0, bs, f, gate=rb.GATE):
     assert np.array_equal(L.counts(), cnt0 + touched.astype(np.uint32))
     assert X1[~touched].tobytes() == X0[~touched].tobytes() and C1[~touched].tobytes() == C0[~touched].tobytes()
     with np.errstate(invalid="ignore"):
-        outlier = rows[np.asarray(ref.chi2 > D * D)]
+        outlier = rows[np.asarray(ref.chi2 > D * D) & (ref.cls != rb.BEHIND)]   # an observation behind the frame is not used at all
     assert len(outlier) == f.n_outlier and not touched[outlier].any()           # all of them gated, none rewritten
     assert np.array_equal(np.isnan(f.chi2), ref.cls == rb.SKIPPED)
     assert np.array_equal(f.cov, f.cov.T)
@@ -170,6 +175,105 @@ def test_solve_and_posterior_against_long_double(n):
 def test_solve_and_posterior_on_one_block(monkeypatch, n):
     monkeypatch.setenv("SBA_RESECT_GRID", "1")
     _run_solve(n, False)
+
+
+# ---- 2b. planted rows of every class ---------------------------------------------------------------------------------------------
+def _displaced(y, angle):
+    """y turned by `angle` about an axis across it."""
+    k = np.cross(y, [0.3, -0.5, 0.8])
+    k = k / np.linalg.norm(k)
+    return y * np.cos(angle) + np.cross(k, y) * np.sin(angle)
+
+
+def _plant(n):
+    """tests/test_gpu_landmark_register.py's 14 planted rows on the robust solve scene, whose every tenth bearing is a wrong match
+    already: five skipped kinds, one behind, eight more displaced bearings."""
+    s = rb.solve_scene(n)
+    X, cov, y = s.X.copy(), s.cov.copy(), s.y.copy()
+    at = lambda frac: min(n - 1, int(frac * n))
+    skipped = {"inf row": at(0.01), "NaN in X": at(0.26), "NaN in Sigma": at(0.34), "negative variance": at(0.51), "zero bearing": n - 1}
+    cov[skipped["inf row"]] = [np.inf, np.inf, np.inf, 0, 0, 0]
+    X[skipped["NaN in X"], 2] = np.nan
+    cov[skipped["NaN in Sigma"], 5] = np.nan
+    cov[skipped["negative variance"]] = [-1e-4, -2e-4, -1e-4, 0, 0, 0]
+    y[skipped["zero bearing"]] = 0.0
+    behind = at(0.68)
+    y[behind] = -y[behind]
+    gated = [at(v) for v in (0.02, 0.13, 0.27, 0.40, 0.55, 0.70, 0.85, 0.99)]
+    for i in gated:
+        y[i] = _displaced(s.y[i], 0.2)
+    planted = sorted(set(skipped.values()) | {behind} | set(gated))
+    assert len(planted) == 14
+    return s, X, cov, y, sorted(skipped.values()), behind, gated, planted
+
+
+@pytest.mark.parametrize("n,grid", [(513, None), (1537, "1")])
+def test_planted_rows_of_every_class(monkeypatch, n, grid):
+    """SKIPPED and BEHIND rows among the wrong matches, through the robust accumulate's own selection of the observations it does
+    not use: at the given pose the counts are exact, chi2 is NaN exactly on the skipped rows, the planted rows and their counts
+    are untouched byte for byte; then the solve against the reference's minimiser over the same rows, and one evaluation."""
+    if grid:
+        monkeypatch.setenv("SBA_RESECT_GRID", grid)
+    s, X, cov, y, skipped, behind, gated, planted = _plant(n)
+    bs = s.bearing_sigma
+    rot, tran = s.truth.rot, s.truth.tran
+    idx = np.array(sorted(set(planted) | set(range(0, n, 4))), dtype=np.int64)
+    zeros = np.zeros(n, dtype=np.uint32)
+    with np.errstate(all="ignore"):
+        noise, cls = lr.freeze(X, cov, y, s.rot0, s.tran0, bs)
+        rot_r, tran_r, eq_r, _ = rb.solve(X, cov, y, noise, s.rot0, s.tran0, D)
+        noise_i, _ = lr.freeze(X[idx], cov[idx], y[idx], s.rot0, s.tran0, bs)
+        eq_i = rb.evaluate(X[idx], cov[idx], y[idx], noise_i, s.rot0, s.tran0, D)
+        eq_0 = rb.evaluate(X, cov, y, noise, s.rot0, s.tran0, D)
+    assert np.array_equal(np.flatnonzero(cls == lr.SKIPPED), skipped) and np.array_equal(np.flatnonzero(cls == lr.BEHIND), [behind])
+    with api.Landmarks(0) as L:
+        for form, ii in (("dense", None), ("indexed", idx)):
+            rows = np.arange(n) if ii is None else ii
+            L.set(X, cov)
+            X0, C0 = L.get()
+            f = L.register_robust(y[rows], rot, tran, D, bs, idx=ii, options=_at_pose(), return_chi2=True)
+            assert f.summary.num_evaluations == 1 and np.array_equal(f.rot, rot) and np.array_equal(f.tran, tran), form
+            with np.errstate(all="ignore"):
+                ref, err, bound = _check_posterior(L, X0, C0, zeros, y[rows], ii, rot, tran, bs, f)
+            print(f"n = {n} {form} at the given pose: counts {_counts(f)}, used {f.n_used}, outliers {f.n_outlier}, errors {err}, bounds {bound}")
+            where = {int(r): j for j, r in enumerate(rows)}
+            assert all(ref.cls[where[i]] == rb.SKIPPED for i in skipped) and ref.cls[where[behind]] == rb.BEHIND
+            assert all(ref.cls[where[i]] == rb.GATED for i in gated)
+            assert f.n_skipped == 5 and f.n_behind == 1 and f.n_used == len(rows) - 6 and f.n_gated >= 8
+            assert f.n_outlier == ref.eq.n_outlier and f.n_outlier >= 8
+            assert np.array_equal(np.flatnonzero(np.isnan(f.chi2)), np.array([where[i] for i in skipped]))
+            X1, C1 = L.get()
+            for i in planted:
+                assert X1[i].tobytes() == X0[i].tobytes() and C1[i].tobytes() == C0[i].tobytes(), (form, i)
+            assert not L.counts()[planted].any(), form
+        # the solve from the start, dense: the users' case
+        L.set(X, cov)
+        X0, C0 = L.get()
+        f = L.register_robust(y, s.rot0, s.tran0, D, bs, options=_tight(), return_chi2=True)
+        dp = np.concatenate([f.rot - rot_r, f.tran - tran_r])
+        maha2 = float(dp @ eq_r.H @ dp)
+        print(f"n = {n} solved: {f.summary.termination} after {f.summary.num_iterations} iterations, (p - p*)^T H (p - p*) = {maha2:.3e}, "
+              f"counts {_counts(f)}, outliers {f.n_outlier}")
+        assert maha2 <= 1e-6
+        with np.errstate(all="ignore"):
+            ref, _, _ = _check_posterior(L, X0, C0, zeros, y, None, s.rot0, s.tran0, bs, f)
+        assert f.n_skipped == 5 and f.n_behind == 1 and f.n_used == n - 6
+        assert all(ref.cls[i] == rb.GATED for i in gated)
+        assert np.array_equal(np.flatnonzero(np.isnan(f.chi2)), np.array(skipped))
+        X1, C1 = L.get()
+        for i in planted:
+            assert X1[i].tobytes() == X0[i].tobytes() and C1[i].tobytes() == C0[i].tobytes(), i
+        assert not L.counts()[planted].any()
+        # one evaluation at the start, both forms
+        L.set(X, cov)
+        for ii, want in ((None, eq_0), (idx, eq_i)):
+            e = L.eval_register_robust(y if ii is None else y[ii], s.rot0, s.tran0, D, bearing_sigma=bs, idx=ii)
+            assert (e.n_used, e.n_behind, e.n_outlier) == (want.n_used, want.n_behind, want.n_outlier)
+            assert e.n_used == (n if ii is None else len(ii)) - 6
+            assert np.isfinite(e.H).all() and np.isfinite(e.g).all() and np.isfinite(e.cost) and np.array_equal(e.H, e.H.T)
+            err = np.array(lr.eq_errors(e, want))
+            print(f"n = {n} evaluation at the start: errors {err}, bounds {_eval_bounds()}")
+            assert (err <= _eval_bounds()).all(), (err, _eval_bounds())
 
 
 # ---- 3. the demonstration --------------------------------------------------------------------------------------------------------
@@ -241,15 +345,22 @@ def test_device_bearings_return_the_host_bearings_bytes(n):
             aligned, shifted = buf[:3 * m], buf[1:]                             # the second one starts 8 bytes off a 16-byte boundary
             for name, t in (("aligned", aligned), ("shifted", shifted)):
                 t.copy_(torch.from_numpy(rows.reshape(-1)))
-                chi2_dev = torch.full((m,), -7.0, dtype=torch.float64, device=dev)
-                torch.cuda.synchronize()
-                A.set(X, cov)
-                B.set(X, cov)
-                host = A.register_robust(rows, s.rot0, s.tran0, idx=ii, return_chi2=True, **kw)
-                got = B.register_robust(None, s.rot0, s.tran0, idx=ii, bearings_device=t.data_ptr(), chi2_device=chi2_dev.data_ptr(), **kw)
-                chi2 = chi2_dev.cpu().numpy()
-                assert _result_bytes(got, chi2) == _result_bytes(host), (form, name)
-                assert _state(A) == _state(B), (form, name)
+                # chi2 between guard cells: 16 bytes in, aligned, two guards on either side; 8 bytes in, off a 16-byte boundary (with
+                # aligned bearings chi2 then goes through the scratch and a device-to-device copy), one guard before and three behind
+                for off in (2, 1):
+                    chi2_dev = torch.full((m + 4,), -7.0, dtype=torch.float64, device=dev)
+                    assert chi2_dev.data_ptr() % 16 == 0
+                    torch.cuda.synchronize()
+                    A.set(X, cov)
+                    B.set(X, cov)
+                    host = A.register_robust(rows, s.rot0, s.tran0, idx=ii, return_chi2=True, **kw)
+                    got = B.register_robust(None, s.rot0, s.tran0, idx=ii, bearings_device=t.data_ptr(), chi2_device=chi2_dev.data_ptr() + 8 * off, **kw)
+                    torch.cuda.synchronize()
+                    all_chi2 = chi2_dev.cpu().numpy()
+                    chi2 = np.ascontiguousarray(all_chi2[off:off + m])
+                    assert (all_chi2[:off] == -7.0).all() and (all_chi2[off + m:] == -7.0).all(), (form, name, off, all_chi2[:off], all_chi2[off + m:])
+                    assert _result_bytes(got, chi2) == _result_bytes(host), (form, name, off)
+                    assert _state(A) == _state(B), (form, name, off)
                 assert torch.equal(t.cpu(), torch.from_numpy(rows.reshape(-1))), (form, name)      # the caller's rows are only read
                 eh = A.eval_register_robust(rows, s.rot0, s.tran0, D, bearing_sigma=1e-3, idx=ii)
                 ed = B.eval_register_robust(None, s.rot0, s.tran0, D, bearing_sigma=1e-3, idx=ii, bearings_device=t.data_ptr())
@@ -382,3 +493,75 @@ def test_empty_map_and_no_observations():
         before = _state(L)
         e = L.eval_register_robust(np.zeros((0, 3)), s.rot0, s.tran0, D, idx=np.zeros(0, dtype=np.int64))
         assert e.n_used == 0 and e.n_outlier == 0 and not e.H.any() and e.cost == 0.0 and _state(L) == before
+
+
+# ---- 6. registration on a map that was edited ------------------------------------------------------------------------------------
+def _register_like_a_fresh_set(L, y, rot, tran):
+    """Every registration entry point on L gives the bytes, and leaves the state, of a fresh handle set from L's rows: prune and
+    append swap the planes and change the size under scratch buffers sized for the map before, and nothing of that may show."""
+    import torch
+    X, Cv = L.get()
+    k = L.counts()
+    n = len(X)
+    y = np.ascontiguousarray(y)
+    y_dev = torch.from_numpy(np.array(y).reshape(-1)).to("cuda:0")
+    torch.cuda.synchronize()
+    plain = api.default_lm_options(huber_delta=0.0, **TIGHT)
+    plain_bytes = lambda f: (b"".join(np.ascontiguousarray(a, dtype=np.float64).tobytes() for a in (f.rot, f.tran, f.cov, f.chi2))
+                             + repr(_counts(f) + (f.n_used,)).encode())
+    with api.Landmarks(0) as T:
+        T.set(X, Cv, 1.0)
+        assert _state(T) == X.tobytes() + Cv.tobytes() + np.zeros(n, dtype=np.uint32).tobytes()
+
+        def alike():
+            X1, C1 = L.get()
+            X2, C2 = T.get()
+            return X1.tobytes() == X2.tobytes() and C1.tobytes() == C2.tobytes() and np.array_equal(L.counts() - k, T.counts())
+
+        a, b = (H.eval_register(y, rot, tran, bearing_sigma=1e-3) for H in (L, T))
+        assert a.H.tobytes() + a.g.tobytes() == b.H.tobytes() + b.g.tobytes() and (a.cost, a.n_used, a.n_behind) == (b.cost, b.n_used, b.n_behind)
+        assert a.n_used > n // 2
+        a, b = (H.eval_register_robust(y, rot, tran, D, bearing_sigma=1e-3) for H in (L, T))
+        assert _eq_bytes(a) == _eq_bytes(b)
+        a, b = (H.eval_register_robust(None, rot, tran, D, bearing_sigma=1e-3, bearings_device=y_dev.data_ptr()) for H in (L, T))
+        assert _eq_bytes(a) == _eq_bytes(b)
+        a, b = (H.register(y, rot, tran, 1e-3, lr.GATE, apply=False, options=plain, return_chi2=True) for H in (L, T))
+        assert plain_bytes(a) == plain_bytes(b) and alike()
+        a, b = (H.register_robust(y, rot, tran, D, 1e-3, apply=False, options=_tight(), return_chi2=True) for H in (L, T))
+        assert _result_bytes(a) == _result_bytes(b) and alike()
+        a, b = (H.register(y, rot, tran, 1e-3, lr.GATE, options=plain, return_chi2=True) for H in (L, T))
+        assert plain_bytes(a) == plain_bytes(b) and alike() and a.n_fused > n // 2
+        chi2 = [torch.full((n + 4,), -7.0, dtype=torch.float64, device="cuda:0") for _ in range(2)]
+        torch.cuda.synchronize()
+        a, b = (H.register_robust(None, rot, tran, D, 1e-3, options=_tight(), bearings_device=y_dev.data_ptr(), chi2_device=c.data_ptr() + 16)
+                for H, c in zip((L, T), chi2))
+        torch.cuda.synchronize()
+        ca, cb = (c.cpu().numpy() for c in chi2)
+        assert (ca[:2] == -7.0).all() and (ca[n + 2:] == -7.0).all()
+        assert _result_bytes(a, ca[2:n + 2]) == _result_bytes(b, cb[2:n + 2]) and alike() and a.n_fused > 0
+        a, b = (H.register_robust(y, rot, tran, D, 1e-3, options=_tight(), return_chi2=True) for H in (L, T))
+        assert _result_bytes(a) == _result_bytes(b) and alike()
+
+
+def test_registration_after_prune_and_append_equals_a_fresh_handle():
+    n = 4097
+    X, cov, frames, (rot, tran) = le.edit_map(n)
+    R = rr.rotmat(rot, np.float64)
+    Xa, Ca = le.extra_rows(513)
+    ya = Xa @ R.T - tran                                                        # the appended landmarks' exact bearings, any length
+    with api.Landmarks(0) as L:
+        L.set(X, cov, le.COV_SCALE)
+        for y, idx in frames:
+            L.fuse(y, rot, tran, 1e-3, lf.GATE, idx=idx)
+        y = frames[0][0]
+        keep = le.mask("alternating", n)
+        assert L.prune(mask=keep).n_kept == 2049                                # the planes have swapped, n is odd
+        y = y[keep]
+        _register_like_a_fresh_set(L, y, rot, tran)
+        L.append(Xa, Ca, le.COV_SCALE)                                          # swapped again, n = 2562 over a scratch sized for 2049
+        y = np.concatenate([y, ya])
+        assert L.size == len(y) == 2562
+        _register_like_a_fresh_set(L, y, rot, tran)
+        keep = le.mask("straddle", L.size)                                      # far below everything sized so far, odd again
+        assert L.prune(mask=keep).n_kept == 75
+        _register_like_a_fresh_set(L, y[keep], rot, tran)
