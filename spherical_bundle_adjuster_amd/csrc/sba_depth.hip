@@ -138,7 +138,7 @@ __device__ __forceinline__ void depth_stream(const Planes& pl, const double* __r
       const double D2 = fmin(fmax(H22, P.min_diagonal), P.max_diagonal);
       // damped 2x2 system (H + D / radius) y = -G; 1 / radius comes from the host, 1 / det is formed once
       const double A11 = __builtin_fma(D1, P.inv_radius, H11), A22 = __builtin_fma(D2, P.inv_radius, H22), A12 = H12;
-      const double inv_det = 1.0 / (A11 * A22 - A12 * A12);
+      const double inv_det = 1.0 / depth_block_det(A11, A22, A12);
       const double y1 = (G2 * A12 - G1 * A22) * inv_det, y2 = (G1 * A12 - G2 * A11) * inv_det;
       const double dl1 = s1 * y1, dl2 = s2 * y2;                               // delta = step .* jacobi scaling
       // Plus(d, alpha * delta) + projection onto d >= 0 (alpha = 1: the trust-region candidate)

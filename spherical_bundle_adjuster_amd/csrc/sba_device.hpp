@@ -56,6 +56,24 @@ struct Planes {
   const double* d2;
 };
 
+// Determinant a d - b^2 of a match's damped 2 x 2 depth block (joint_block, depth_stream), as Kahan's difference of products:
+// the rounding error of b * b is added back, so the result is within 1.5 ulp of the true value and EXACTLY 0 for an exactly
+// singular block (a == d == |b|: parallel rays whose damping D / radius fell below half an ulp of the block).  The plain
+// a * d - b * b is contracted to fma(a, d, -(b * b)) and leaves that rounding error as the "determinant": 1e-17 of a^2 with
+// either sign, a finite reciprocal and a finite, meaningless reduced system or step where the host's step logic is written
+// for a non-finite one (a failed Cholesky factorisation, a model that is not > 0: an invalid step).
+#if defined(__HIPCC__)
+__device__ __forceinline__ double depth_block_det(double a, double d, double b) {
+  double w;
+  {
+#pragma clang fp contract(off)
+    w = b * b;
+  }
+  const double err = __builtin_fma(-b, b, w);      // w - b * b, exact
+  return __builtin_fma(a, d, -w) + err;
+}
+#endif
+
 constexpr int kPackSize = 24;
 constexpr int kRow = 32;   // doubles per block-partial row (256 B: two whole 128-byte lines, 24 used)
 #ifndef SBA_BLOCK

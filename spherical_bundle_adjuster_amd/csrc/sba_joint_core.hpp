@@ -116,7 +116,7 @@ __device__ __forceinline__ void joint_block(const JointParams& P, double x, doub
   b.U22 = __builtin_fma(D2, P.inv_radius, H22);
   b.U12 = b.s1 * h12 * b.s2;
   if (!valid) { b.U11 = 1.0; b.U22 = 1.0; b.U12 = 0.0; }     // the padding match of an odd-sized problem: weight 0, any regular block
-  b.inv_det = 1.0 / (b.U11 * b.U22 - b.U12 * b.U12);
+  b.inv_det = 1.0 / depth_block_det(b.U11, b.U22, b.U12);
   b.G1 = b.s1 * b.gd1; b.G2 = b.s2 * b.gd2;
   const double k1 = b.s1 * b.w, k2 = b.s2 * b.w;
 #pragma unroll
