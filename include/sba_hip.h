@@ -810,6 +810,69 @@ int sba_landmarks_register_robust_device(sba_landmarks* h, const int64_t* idx /*
                                          const double tran0[3], const sba_landmark_register_options* opt,
                                          sba_landmark_register_robust_result* res, void* chi2_out_dev /* double[m], device, or NULL */);
 
+/* ---- the landmark map: the joint registration under a redescending (Hampel) loss ------------------------------------ */
+/* Huber's influence is bounded but not zero: a wrong match far out keeps pulling with |w u| = delta while H_rho counts it with
+ * a small weight, so sba_landmarks_register_robust's Sigma_c is optimistic on frames with wrong matches.  The same objective
+ * F_rho = sum_j rho(chi2_j) under Hampel's three-part loss removes that.  With s = chi2_j, r = sqrt(s), 0 < a < b < c:
+ *     s <= a^2          w = 1                           rho = s
+ *     a^2 < s <= b^2    w = a / r                       rho = 2 a r - a^2
+ *     b^2 < s <= c^2    w = a (c - r) / ((c - b) r)     rho = a (b + c) - a^2 - a (c - r)^2 / (c - b)
+ *     s > c^2           w = 0                           rho = a (b + c) - a^2
+ * w = rho'(s), rho is C1, a = base.lm.huber_delta.  H = sum w J_w^T J_w, g = sum w J_w^T u, cost = 1/2 sum rho as above;
+ * n_outlier = the used observations with s > a^2, n_rejected = those with s > c^2 (weight exactly 0).  b = c = +inf is Huber.
+ * THE WRITE-BACK is sba_landmarks_register_robust's, with Sigma_c = H_rho^-1 and chi2_gate > a^2 refused: Hampel's weight is
+ * exactly 1 up to a, so every fused observation had weight 1 and every downweighted or rejected one is GATED, its landmark
+ * untouched byte for byte.
+ * THE OBJECTIVE IS NOT CONVEX.  With huber_first != 0 the call first runs sba_landmarks_register_robust's solve (delta = a, the
+ * same lm options, the same frozen noise) from rot0 | tran0, reports its pose and iteration count in rot_huber, tran_huber,
+ * huber_iterations, and runs the Hampel solve from there on the same frozen noise; summary is the second solve's.  With
+ * huber_first == 0 the Hampel solve starts at rot0 | tran0 and the three fields are the start pose and 0.
+ * Refusals, all before the first device call with nothing written and the handle usable: everything
+ * sba_landmarks_register_robust refuses, with the same codes (chi2_gate > a^2 among them); b or c NaN, b <= a, c <= b, exactly
+ * one of them infinite: SBA_ERR_INVALID_ARG.  After the freeze the same SBA_ERR_NUMERIC cases, and n_used - n_rejected < 3 at
+ * the solution (fewer than three observations carry weight): SBA_ERR_NUMERIC with the map untouched.  The _device twins as above. */
+typedef struct sba_landmark_register_hampel_options {
+  sba_landmark_register_options base;  /* base.lm.huber_delta = a */
+  double b, c;                 /* finite with a < b < c, or both +inf */
+  int huber_first;             /* != 0: the Huber solve first, the Hampel solve from its minimiser */
+} sba_landmark_register_hampel_options;
+typedef struct sba_landmark_register_hampel_result {
+  double rot[3], tran[3];      /* the solved pose */
+  double cov[36];              /* Sigma_c = H_rho^-1, row-major over [rot | tran] */
+  sba_lm_summary summary;      /* of the Hampel solve */
+  long long n_obs;             /* = n_skipped + n_behind + n_gated + n_fused */
+  long long n_skipped, n_behind, n_gated, n_fused;
+  long long n_used;            /* observations that entered the sums at the solution */
+  long long n_outlier;         /* of which: chi2 > a^2 at the solution */
+  long long n_rejected;        /* of which: chi2 > c^2 at the solution, weight 0 */
+  double rot_huber[3], tran_huber[3];  /* the Huber stage's minimiser, or the start pose */
+  int huber_iterations;        /* the Huber stage's summary.num_iterations, or 0 */
+} sba_landmark_register_hampel_result;
+typedef struct sba_landmark_register_hampel_eval {
+  double H[36];                /* row-major symmetric 6 x 6 over [rot | tran] */
+  double g[6];
+  double cost;
+  long long n_used;            /* observations that entered the sums */
+  long long n_behind;          /* of which: d* <= 0 at the evaluation pose */
+  long long n_outlier;         /* of which: chi2 > a^2 */
+  long long n_rejected;        /* of which: chi2 > c^2 */
+} sba_landmark_register_hampel_eval;
+int sba_landmarks_eval_register_hampel(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */,
+                                       size_t m, const double rot[3], const double tran[3], const double rot_ref[3],
+                                       const double tran_ref[3], const sba_landmark_register_hampel_options* opt,
+                                       sba_landmark_register_hampel_eval* eval);
+int sba_landmarks_register_hampel(sba_landmarks* h, const int64_t* idx /* [m] or NULL */, const double* bearings /* double[3 m] */,
+                                  size_t m, const double rot0[3], const double tran0[3], const sba_landmark_register_hampel_options* opt,
+                                  sba_landmark_register_hampel_result* res, double* chi2_out /* [m] or NULL */);
+int sba_landmarks_eval_register_hampel_device(sba_landmarks* h, const int64_t* idx /* [m], host, or NULL */,
+                                              const void* bearings_dev /* double[3 m], device */, size_t m, const double rot[3],
+                                              const double tran[3], const double rot_ref[3], const double tran_ref[3],
+                                              const sba_landmark_register_hampel_options* opt, sba_landmark_register_hampel_eval* eval);
+int sba_landmarks_register_hampel_device(sba_landmarks* h, const int64_t* idx /* [m], host, or NULL */,
+                                         const void* bearings_dev /* double[3 m], device */, size_t m, const double rot0[3],
+                                         const double tran0[3], const sba_landmark_register_hampel_options* opt,
+                                         sba_landmark_register_hampel_result* res, void* chi2_out_dev /* double[m], device, or NULL */);
+
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other
  * ranks by any host channel, then every rank calls sba_problem_comm_init_rank.  After that

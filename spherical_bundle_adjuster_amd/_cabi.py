@@ -153,6 +153,19 @@ class LandmarkRegisterRobustEval(C.Structure):
     _fields_ = LandmarkRegisterEval._fields_ + [("n_outlier", C.c_longlong)]
 
 
+class LandmarkRegisterHampelOptions(C.Structure):
+    _fields_ = [("base", LandmarkRegisterOptions), ("b", C.c_double), ("c", C.c_double), ("huber_first", C.c_int)]
+
+
+class LandmarkRegisterHampelResult(C.Structure):
+    _fields_ = LandmarkRegisterRobustResult._fields_ + [("n_rejected", C.c_longlong), ("rot_huber", C.c_double * 3),
+                                                        ("tran_huber", C.c_double * 3), ("huber_iterations", C.c_int)]
+
+
+class LandmarkRegisterHampelEval(C.Structure):
+    _fields_ = LandmarkRegisterRobustEval._fields_ + [("n_rejected", C.c_longlong)]
+
+
 ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
@@ -249,6 +262,14 @@ SIGNATURES = {
                                                             C.POINTER(LandmarkRegisterOptions), C.POINTER(LandmarkRegisterRobustEval)]),
     "sba_landmarks_register_robust_device": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.c_size_t, _dp, _dp,
                                                        C.POINTER(LandmarkRegisterOptions), C.POINTER(LandmarkRegisterRobustResult), _vp]),
+    "sba_landmarks_eval_register_hampel": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp, _dp, _dp,
+                                                     C.POINTER(LandmarkRegisterHampelOptions), C.POINTER(LandmarkRegisterHampelEval)]),
+    "sba_landmarks_register_hampel": (C.c_int, [_vp, C.POINTER(C.c_int64), _dp, C.c_size_t, _dp, _dp,
+                                                C.POINTER(LandmarkRegisterHampelOptions), C.POINTER(LandmarkRegisterHampelResult), _dp]),
+    "sba_landmarks_eval_register_hampel_device": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.c_size_t, _dp, _dp, _dp, _dp,
+                                                            C.POINTER(LandmarkRegisterHampelOptions), C.POINTER(LandmarkRegisterHampelEval)]),
+    "sba_landmarks_register_hampel_device": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.c_size_t, _dp, _dp,
+                                                       C.POINTER(LandmarkRegisterHampelOptions), C.POINTER(LandmarkRegisterHampelResult), _vp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

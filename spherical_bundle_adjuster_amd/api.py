@@ -159,6 +159,23 @@ class LandmarkRobustRegistration(LandmarkRegistration):
 
 
 @dataclass
+class LandmarkHampelRegisterEquations(LandmarkRobustRegisterEquations):
+    """One evaluation of the joint registration under Hampel's redescending loss (Landmarks.eval_register_hampel) with the
+    thresholds a = huber_delta < b < c on sqrt(chi2): weight 1 up to a, a / r up to b, falling to exactly 0 at c."""
+    n_rejected: int        # of the used observations: chi2 > c^2, weight 0
+
+
+@dataclass
+class LandmarkHampelRegistration(LandmarkRobustRegistration):
+    """What one Landmarks.register_hampel did: LandmarkRobustRegistration under Hampel's loss; cov = H_rho^-1, in which a rejected
+    observation does not count at all."""
+    n_rejected: int        # observations with chi2 > c^2 at the solution
+    rot_huber: np.ndarray  # (3,) the Huber stage's minimiser (huber_first), else the start pose
+    tran_huber: np.ndarray # (3,)
+    huber_iterations: int  # LM iterations of the Huber stage, 0 without it
+
+
+@dataclass
 class LandmarkPrune:
     """What one Landmarks.prune did: every landmark falls into exactly one class, tested in this order, n_before = n_invalid +
     n_uncertain + n_unobserved + n_masked + n_kept.  invalid: a non-finite entry of X or Sigma or a negative variance; uncertain:
@@ -1228,6 +1245,65 @@ class Landmarks:
                                           np.array(res.cov, dtype=np.float64).reshape(6, 6), _summary(res.summary), int(res.n_obs),
                                           int(res.n_skipped), int(res.n_behind), int(res.n_gated), int(res.n_fused), int(res.n_used), chi2,
                                           int(res.n_outlier))
+
+    def _hampel_options(self, opt, huber_delta, b, c, huber_first):
+        """The Hampel options record around the robust one: b and c default to 2 a and 4 a."""
+        ho = cabi.LandmarkRegisterHampelOptions()
+        ho.base = opt
+        ho.b = 2.0 * float(huber_delta) if b is None else float(b)
+        ho.c = 4.0 * float(huber_delta) if c is None else float(c)
+        ho.huber_first = 1 if huber_first else 0
+        return ho
+
+    def eval_register_hampel(self, bearings, rot, tran, huber_delta: float, b: float | None = None, c: float | None = None, rot_ref=None,
+                             tran_ref=None, bearing_sigma: float = 0.0, idx=None, bearings_device=None,
+                             m: int | None = None) -> LandmarkHampelRegisterEquations:
+        """eval_register under Hampel's three-part loss on every landmark's chi2: a = huber_delta < b < c in units of the whitened
+        residual, by default b = 2 a and c = 4 a; b = c = inf is the Huber loss.  Everything else as for eval_register_robust."""
+        ptr, m, ii, opt, keep = self._robust_args(bearings, bearings_device, m, idx, huber_delta, bearing_sigma, None, False, None)
+        ho = self._hampel_options(opt, huber_delta, b, c, True)
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        rot_ref = rot if rot_ref is None else _f64(rot_ref, (3,))
+        tran_ref = tran if tran_ref is None else _f64(tran_ref, (3,))
+        ev = cabi.LandmarkRegisterHampelEval()
+        fn = self._lib.sba_landmarks_eval_register_hampel if bearings_device is None else self._lib.sba_landmarks_eval_register_hampel_device
+        cabi.check(self._lib, fn(self._h, None if ii is None else ii.ctypes.data_as(C.POINTER(C.c_int64)), ptr, m, _dptr(rot), _dptr(tran),
+                                 _dptr(rot_ref), _dptr(tran_ref), C.byref(ho), C.byref(ev)))
+        return LandmarkHampelRegisterEquations(np.array(ev.H, dtype=np.float64).reshape(6, 6), np.array(ev.g, dtype=np.float64), float(ev.cost),
+                                               int(ev.n_used), int(ev.n_behind), int(ev.n_outlier), int(ev.n_rejected))
+
+    def register_hampel(self, bearings, rot, tran, huber_delta: float, b: float | None = None, c: float | None = None,
+                        huber_first: bool = True, bearing_sigma: float = 0.0, chi2_gate: float | None = None, idx=None, apply: bool = True,
+                        options: cabi.LmOptions | None = None, return_chi2: bool = False, bearings_device=None, m: int | None = None,
+                        chi2_device=None) -> LandmarkHampelRegistration:
+        """`register_robust` under Hampel's redescending loss: a wrong match beyond c has weight exactly 0, in the solve and in
+        cov = H_rho^-1, which Huber's bounded but non-zero influence leaves optimistic.  a = huber_delta, b and c default to 2 a
+        and 4 a.  The objective is not convex: with huber_first the Huber solve runs first, from (rot, tran), and the Hampel solve
+        starts at its minimiser (rot_huber, tran_huber, huber_iterations report that stage).  chi2_gate defaults to a^2, the
+        largest value accepted.  Raises SbaError(SBA_ERR_NUMERIC), the map untouched, when fewer than 3 observations keep a
+        weight at the solution.  Everything else as for register_robust."""
+        ptr, m, ii, opt, keep = self._robust_args(bearings, bearings_device, m, idx, huber_delta, bearing_sigma, chi2_gate, apply, options)
+        ho = self._hampel_options(opt, huber_delta, b, c, huber_first)
+        rot, tran = _f64(rot, (3,)), _f64(tran, (3,))
+        res = cabi.LandmarkRegisterHampelResult()
+        ip = None if ii is None else ii.ctypes.data_as(C.POINTER(C.c_int64))
+        if bearings_device is None:
+            if chi2_device is not None:
+                raise ValueError("chi2_device goes with bearings_device")
+            chi2 = np.full(m, np.nan) if return_chi2 else None
+            cabi.check(self._lib, self._lib.sba_landmarks_register_hampel(
+                self._h, ip, ptr, m, _dptr(rot), _dptr(tran), C.byref(ho), C.byref(res), None if chi2 is None else _dptr(chi2)))
+        else:
+            if return_chi2:
+                raise ValueError("with bearings_device chi2 is written to chi2_device")
+            chi2 = chi2_device
+            cabi.check(self._lib, self._lib.sba_landmarks_register_hampel_device(
+                self._h, ip, ptr, m, _dptr(rot), _dptr(tran), C.byref(ho), C.byref(res), C.c_void_p(int(chi2_device) if chi2_device else 0)))
+        return LandmarkHampelRegistration(np.array(res.rot, dtype=np.float64), np.array(res.tran, dtype=np.float64),
+                                          np.array(res.cov, dtype=np.float64).reshape(6, 6), _summary(res.summary), int(res.n_obs),
+                                          int(res.n_skipped), int(res.n_behind), int(res.n_gated), int(res.n_fused), int(res.n_used), chi2,
+                                          int(res.n_outlier), int(res.n_rejected), np.array(res.rot_huber, dtype=np.float64),
+                                          np.array(res.tran_huber, dtype=np.float64), int(res.huber_iterations))
 
     # -- edits: the counts survive all of them -------------------------------------------------------
     def scores(self) -> np.ndarray:

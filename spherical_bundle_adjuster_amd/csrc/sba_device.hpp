@@ -545,6 +545,15 @@ hipError_t launch_landmarks_register_robust_reduce(const LandmarkPlanes& pl, con
                                                    const long long* idx, const double* bearings, const double* noise, double* partials, int grid,
                                                    double* out, hipStream_t stream);
 
+// The same pass under Hampel's redescending loss (sba_landmarks_register_hampel.hip; the loss, LandmarkRegisterHampel and the
+// per-observation code: sba_landmarks_register_hampel.hpp): a row of 32 slots, the SBA_RESECT_* ones and the count of the
+// observations beyond c in slot SBA_HAMPEL_NREJ.  The freeze and the write-back are again the two launches above.
+struct LandmarkRegisterHampel;
+hipError_t landmarks_register_hampel_blocks_per_cu(bool indexed, int* blocks);   // resident 256-thread blocks per CU
+hipError_t launch_landmarks_register_hampel_reduce(const LandmarkPlanes& pl, const LandmarkRegisterParams& prm, const LandmarkRegisterHampel& loss,
+                                                   const long long* idx, const double* bearings, const double* noise, double* partials, int grid,
+                                                   double* out, hipStream_t stream);
+
 // Edits of the landmark map (sba_landmarks_edit.hip; the score, the classes of a prune and the checks: sba_landmarks_edit.hpp).
 // Scores: out [elems] doubles (device, 16-byte aligned).  Keep: one streaming pass that writes keep[ntiles * kCompactTile] bytes
 // (1 = kept, 0 beyond n) and adds the LANDMARK_PRUNE_CLASSES class counts to `counters` (zeroed by the launcher):

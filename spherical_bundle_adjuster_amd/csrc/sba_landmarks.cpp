@@ -4,7 +4,8 @@
 // index checks: sba_landmarks.hpp.  Below them the edits of the map -- scores, prune, append, gather -- with their kernels in
 // sba_landmarks_edit.hip and their checks in sba_landmarks_edit.hpp, and at the end the joint registration of a frame -- its pose
 // and its landmarks solved together -- with its kernels in sba_landmarks_register.hip and its per-observation code in
-// sba_landmarks_register.hpp, and last its robust form (sba_landmarks_register_robust.hpp, sba_landmarks_register_robust.hip).
+// sba_landmarks_register.hpp, then its robust form (sba_landmarks_register_robust.hpp, sba_landmarks_register_robust.hip) and
+// last that form under Hampel's redescending loss (sba_landmarks_register_hampel.hpp, sba_landmarks_register_hampel.hip).
 // Every wait is the bounded stream_wait; a handle whose wait gave up is poisoned.
 #include <algorithm>
 #include <chrono>
@@ -20,6 +21,7 @@
 #include "sba_landmarks_edit.hpp"
 #include "sba_landmarks_register.hpp"
 #include "sba_landmarks_register_robust.hpp"
+#include "sba_landmarks_register_hampel.hpp"
 #include "sba_lm.hpp"
 
 struct sba_landmarks {
@@ -50,6 +52,7 @@ struct sba_landmarks {
   size_t reg_bytes = 0;
   int occ_reg[sba::LANDMARK_REGISTER_KERNELS][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};   // per [kernel][indexed][apply]
   int occ_reg_robust[2] = {0, 0};          // ... of landmarks_register_robust_reduce_kernel per [indexed]
+  int occ_reg_hampel[2] = {0, 0};          // ... of landmarks_register_hampel_reduce_kernel per [indexed]
 };
 
 namespace {
@@ -936,6 +939,215 @@ int sba_landmarks_register_robust_device(sba_landmarks* h, const int64_t* idx, c
                                          const double tran0[3], const sba_landmark_register_options* opt, sba_landmark_register_robust_result* res,
                                          void* chi2_out_dev) {
   return register_robust_common(h, idx, static_cast<const double*>(bearings_dev), true, m, rot0, tran0, opt, res, static_cast<double*>(chi2_out_dev));
+}
+
+}  // extern "C"
+
+// ---- the joint registration under Hampel's redescending loss (sba_landmarks_register_hampel.hpp) -------------------------------------
+namespace {
+
+int register_hampel_occ(sba_landmarks* h, bool indexed, int* occ) {
+  return cached_occ(&h->occ_reg_hampel[indexed ? 1 : 0], [&](int* o) { return sba::landmarks_register_hampel_blocks_per_cu(indexed, o); }, occ);
+}
+
+// The refusals of the four Hampel entry points, all before the first device call: robust_check's with the same codes, then the
+// thresholds b and c.
+int hampel_check(sba_landmarks* h, const int64_t* idx, const void* bearings, size_t m, const double* rot, const double* tran, const double* rot_ref,
+                 const double* tran_ref, const sba_landmark_register_hampel_options* opt, const void* out, bool on_device, const void* chi2_out) {
+  if (!opt) return sba::set_error(SBA_ERR_INVALID_ARG, "null argument");
+  const int rc = robust_check(h, idx, bearings, m, rot, tran, rot_ref, tran_ref, &opt->base, out, on_device, chi2_out);
+  if (rc) return rc;
+  if (const char* why = sba::landmark_register_check_hampel(opt->base.lm.huber_delta, opt->b, opt->c, opt->base.chi2_gate))
+    return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
+  return SBA_OK;
+}
+
+// robust_freeze, then the grid of the Hampel reduce pass by the same rule from landmarks_register_hampel_reduce_kernel's two
+// occupancies.  w->grid_reduce stays the robust pass's, so that the Huber stage runs sba_landmarks_register_robust's very
+// launches.  The block rows of both passes share the scratch, which is grown for the larger grid BEFORE robust_freeze lays it out.
+int hampel_freeze(sba_landmarks* h, const int64_t* idx, const double* bearings, bool on_device, size_t m, const double rot_ref[3],
+                  const double tran_ref[3], double bearing_sigma, RegisterWork* w, int* grid_hampel) {
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  const bool indexed = idx != nullptr;
+  int occ = 1, occ_other = 1;
+  int rc = register_hampel_occ(h, indexed, &occ);
+  if (rc) return rc;
+  rc = register_hampel_occ(h, !indexed, &occ_other);
+  if (rc) return rc;
+  *grid_hampel = grid_for(h, indexed ? (m + 1) / 2 : h->elems / 2, std::min(occ, occ_other));
+  rc = grow_scratch(&h->reg, &h->reg_bytes, kCounterBytes + (static_cast<size_t>(*grid_hampel) + 1) * sba::JOINT_ROW * sizeof(double));
+  if (rc) return rc;
+  return robust_freeze(h, idx, bearings, on_device, m, rot_ref, tran_ref, bearing_sigma, w);
+}
+
+int hampel_reduce_pass(sba_landmarks* h, const RegisterWork& w, int grid, const sba::LandmarkRegisterHampel& loss, const double rot[3],
+                       const double tran[3], double* row) {
+  sba::LandmarkRegisterParams prm;
+  sba::landmark_register_fill(h->n, w.m, rot, tran, nullptr, w.bearing_sigma, INFINITY, &prm);
+  SBA_TRY_HIP(sba::launch_landmarks_register_hampel_reduce(planes_of(h), prm, loss, w.indexed ? w.obs.idx : nullptr, w.obs.bearings, w.obs.noise,
+                                                           w.partials, grid, w.row_dev, h->stream));
+  SBA_TRY_HIP(hipMemcpyAsync(row, w.row_dev, sba::SBA_HAMPEL_COUNT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return sba::stream_wait(h->stream, "Hampel landmark registration reduce pass", &h->poisoned);
+}
+
+int eval_register_hampel_common(sba_landmarks* h, const int64_t* idx, const double* bearings, bool on_device, size_t m, const double rot[3],
+                                const double tran[3], const double rot_ref[3], const double tran_ref[3],
+                                const sba_landmark_register_hampel_options* opt, sba_landmark_register_hampel_eval* eval) {
+  int rc = hampel_check(h, idx, bearings, m, rot, tran, rot_ref, tran_ref, opt, eval, on_device, nullptr);
+  if (rc) return rc;
+  *eval = sba_landmark_register_hampel_eval{};
+  if (h->n == 0 || m == 0) return SBA_OK;
+  RegisterWork w;
+  int grid = 0;
+  rc = hampel_freeze(h, idx, bearings, on_device, m, rot_ref, tran_ref, opt->base.bearing_sigma, &w, &grid);
+  if (rc) return rc;
+  sba::LandmarkRegisterHampel loss;
+  sba::landmark_register_hampel_fill(opt->base.lm.huber_delta, opt->b, opt->c, &loss);
+  double row[sba::JOINT_ROW] = {0};
+  rc = hampel_reduce_pass(h, w, grid, loss, rot, tran, row);
+  if (rc) return rc;
+  if (!sba::resect_row_finite(row)) return sba::set_error(SBA_ERR_NUMERIC, "non-finite registration sums");
+  sba_normal_eq ne;
+  double n_behind = 0.0;
+  sba::resect_expand_row(row, &ne, &n_behind);
+  std::memcpy(eval->H, ne.H, sizeof(ne.H));
+  std::memcpy(eval->g, ne.g, sizeof(ne.g));
+  eval->cost = ne.cost;
+  eval->n_used = static_cast<long long>(ne.sum_w);
+  eval->n_behind = static_cast<long long>(n_behind);
+  eval->n_outlier = static_cast<long long>(ne.n_outlier);
+  eval->n_rejected = static_cast<long long>(row[sba::SBA_HAMPEL_NREJ]);
+  return SBA_OK;
+}
+
+int register_hampel_common(sba_landmarks* h, const int64_t* idx, const double* bearings, bool on_device, size_t m, const double rot0[3],
+                           const double tran0[3], const sba_landmark_register_hampel_options* opt, sba_landmark_register_hampel_result* res,
+                           double* chi2_out) {
+  int rc = hampel_check(h, idx, bearings, m, rot0, tran0, rot0, tran0, opt, res, on_device, chi2_out);
+  if (rc) return rc;
+  *res = sba_landmark_register_hampel_result{};
+  for (int a = 0; a < 3; ++a) { res->rot[a] = res->rot_huber[a] = rot0[a]; res->tran[a] = res->tran_huber[a] = tran0[a]; }
+  if (h->n == 0 || m == 0) return SBA_OK;
+  const auto t_start = std::chrono::steady_clock::now();
+  const sba_landmark_register_options& base = opt->base;
+  RegisterWork w;
+  int grid = 0;
+  rc = hampel_freeze(h, idx, bearings, on_device, m, rot0, tran0, base.bearing_sigma, &w, &grid);
+  if (rc) return rc;
+  if (w.freeze_counts[sba::LANDMARK_LIVE] < 3)
+    return sba::set_error(SBA_ERR_NUMERIC, "pose not determined: %lld observations take part after the freeze (%lld skipped, %lld behind), 3 are needed",
+                          w.freeze_counts[sba::LANDMARK_LIVE], w.freeze_counts[sba::LANDMARK_SKIPPED], w.freeze_counts[sba::LANDMARK_BEHIND]);
+  sba::LandmarkRegisterRobust huber_loss;
+  sba::landmark_register_robust_fill(base.lm.huber_delta, &huber_loss);
+  sba::LandmarkRegisterHampel loss;
+  sba::landmark_register_hampel_fill(base.lm.huber_delta, opt->b, opt->c, &loss);
+  struct Visit { double rot[3], tran[3], H[36], n_used, n_outlier, n_rejected; };
+  std::vector<Visit> visits;
+  double seconds_eval = 0.0;
+  int eval_rc = SBA_OK;
+  bool hampel_stage = false;
+  auto evaluate = [&](const double r[3], const double t[3], sba_normal_eq* ne) -> bool {
+    const auto t0 = std::chrono::steady_clock::now();
+    double row[sba::JOINT_ROW] = {0};
+    eval_rc = hampel_stage ? hampel_reduce_pass(h, w, grid, loss, r, t, row) : robust_reduce_pass(h, w, huber_loss, r, t, row);
+    seconds_eval += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (eval_rc) return false;
+    if (!sba::resect_row_finite(row)) return false;
+    sba::resect_expand_row(row, ne, nullptr);
+    Visit v;
+    for (int a = 0; a < 3; ++a) { v.rot[a] = r[a]; v.tran[a] = t[a]; }
+    std::memcpy(v.H, ne->H, sizeof(v.H));
+    v.n_used = ne->sum_w;
+    v.n_outlier = ne->n_outlier;
+    v.n_rejected = row[sba::SBA_HAMPEL_NREJ];
+    visits.push_back(v);
+    return true;
+  };
+  double r[3] = {rot0[0], rot0[1], rot0[2]}, t[3] = {tran0[0], tran0[1], tran0[2]};
+  sba_lm_summary sum;
+  int huber_iterations = 0;
+  if (opt->huber_first) {
+    // stage 1: sba_landmarks_register_robust's solve -- its kernel, its grid, its options -- from the start pose
+    std::memset(&sum, 0, sizeof(sum));
+    const int status = sba::lm_solve(SBA_MODE_RT, r, t, base.lm, evaluate, &sum);
+    if (eval_rc) return eval_rc;
+    if (status != SBA_OK) return sba::set_error(status, "Hampel joint registration: the Huber stage failed: non-finite sums or 5 consecutive invalid steps");
+    huber_iterations = sum.num_iterations;
+    visits.clear();
+  }
+  const double r_huber[3] = {r[0], r[1], r[2]}, t_huber[3] = {t[0], t[1], t[2]};
+  // stage 2: the Hampel solve from there, on the same frozen noise
+  hampel_stage = true;
+  seconds_eval = 0.0;
+  std::memset(&sum, 0, sizeof(sum));
+  const int status = sba::lm_solve(SBA_MODE_RT, r, t, base.lm, evaluate, &sum);
+  if (eval_rc) return eval_rc;
+  sum.seconds_eval = seconds_eval;
+  if (status != SBA_OK) return sba::set_error(status, "Hampel joint registration solve failed: non-finite sums or 5 consecutive invalid steps");
+  const Visit* at = nullptr;
+  for (size_t k = visits.size(); k-- > 0;)
+    if (std::memcmp(visits[k].rot, r, sizeof(r)) == 0 && std::memcmp(visits[k].tran, t, sizeof(t)) == 0) { at = &visits[k]; break; }
+  if (at && at->n_used - at->n_rejected < 3.0)
+    return sba::set_error(SBA_ERR_NUMERIC, "pose not determined: %lld of the %lld observations at the solution lie beyond c and carry no weight, 3 with weight are needed",
+                          static_cast<long long>(at->n_rejected), static_cast<long long>(at->n_used));
+  double cov[36];
+  if (!at || !sba::resect_cov_inverse(at->H, cov))
+    return sba::set_error(SBA_ERR_NUMERIC, "pose not determined: the reduced normal matrix is not positive definite at the solution");
+  // the write-back at the solution: sba_landmarks_register's, with Sigma_c = H_rho^-1
+  const bool apply = base.apply != 0;
+  int occ = 1;
+  rc = register_occ(h, sba::LANDMARK_REGISTER_APPLY, w.indexed, apply, &occ);
+  if (rc) return rc;
+  // chi2 on the device goes straight to the caller where the pass's stores fit (dense_vectors_fit), else through the scratch
+  const bool chi2_direct = on_device && chi2_out && (w.indexed || dense_vectors_fit(chi2_out, m));
+  double* chi2_dev = !chi2_out ? nullptr : (chi2_direct ? chi2_out : w.obs.chi2);
+  sba::LandmarkRegisterParams prm;
+  sba::landmark_register_fill(h->n, m, r, t, cov, base.bearing_sigma, base.chi2_gate, &prm);
+  SBA_TRY_HIP(sba::launch_landmarks_register_apply(planes_of(h), prm, w.indexed ? w.obs.idx : nullptr, w.obs.bearings, w.obs.noise, chi2_dev,
+                                                   w.obs.counters, apply, grid_for(h, w.indexed ? m : h->elems / 2, occ), h->stream));
+  unsigned long long host_counts[sba::LANDMARK_CLASSES] = {0, 0, 0, 0};
+  SBA_TRY_HIP(hipMemcpyAsync(host_counts, w.obs.counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
+  if (chi2_out && !chi2_direct)
+    SBA_TRY_HIP(hipMemcpyAsync(chi2_out, w.obs.chi2, m * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "Hampel landmark registration write-back", &h->poisoned);
+  if (rc) return rc;
+  for (int a = 0; a < 3; ++a) { res->rot[a] = r[a]; res->tran[a] = t[a]; res->rot_huber[a] = r_huber[a]; res->tran_huber[a] = t_huber[a]; }
+  std::memcpy(res->cov, cov, sizeof(cov));
+  counts_to_result(host_counts, res);
+  res->n_used = static_cast<long long>(at->n_used);
+  res->n_outlier = static_cast<long long>(at->n_outlier);
+  res->n_rejected = static_cast<long long>(at->n_rejected);
+  res->huber_iterations = huber_iterations;
+  sum.seconds_total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+  res->summary = sum;
+  return SBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sba_landmarks_eval_register_hampel(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double rot[3],
+                                       const double tran[3], const double rot_ref[3], const double tran_ref[3],
+                                       const sba_landmark_register_hampel_options* opt, sba_landmark_register_hampel_eval* eval) {
+  return eval_register_hampel_common(h, idx, bearings, false, m, rot, tran, rot_ref, tran_ref, opt, eval);
+}
+
+int sba_landmarks_register_hampel(sba_landmarks* h, const int64_t* idx, const double* bearings, size_t m, const double rot0[3], const double tran0[3],
+                                  const sba_landmark_register_hampel_options* opt, sba_landmark_register_hampel_result* res, double* chi2_out) {
+  return register_hampel_common(h, idx, bearings, false, m, rot0, tran0, opt, res, chi2_out);
+}
+
+int sba_landmarks_eval_register_hampel_device(sba_landmarks* h, const int64_t* idx, const void* bearings_dev, size_t m, const double rot[3],
+                                              const double tran[3], const double rot_ref[3], const double tran_ref[3],
+                                              const sba_landmark_register_hampel_options* opt, sba_landmark_register_hampel_eval* eval) {
+  return eval_register_hampel_common(h, idx, static_cast<const double*>(bearings_dev), true, m, rot, tran, rot_ref, tran_ref, opt, eval);
+}
+
+int sba_landmarks_register_hampel_device(sba_landmarks* h, const int64_t* idx, const void* bearings_dev, size_t m, const double rot0[3],
+                                         const double tran0[3], const sba_landmark_register_hampel_options* opt, sba_landmark_register_hampel_result* res,
+                                         void* chi2_out_dev) {
+  return register_hampel_common(h, idx, static_cast<const double*>(bearings_dev), true, m, rot0, tran0, opt, res, static_cast<double*>(chi2_out_dev));
 }
 
 }  // extern "C"
