@@ -25,7 +25,9 @@
  *   - (no counterpart in the reference) the landmarks kept across frames and improved by each registered frame's bearings
  *       -> sba_landmarks_*()               (a handle of its own; sba_landmarks_fuse: one Kalman update per landmark;
  *                                           sba_landmarks_scores / _prune / _append / _gather: the map edited on the device;
- *                                           sba_landmarks_register: a frame's pose and its landmarks solved jointly)
+ *                                           sba_landmarks_register: a frame's pose and its landmarks solved jointly;
+ *                                           sba_landmarks_set_descriptors / _associate: a descriptor row per landmark and a
+ *                                           frame's idx and bearings from its descriptors)
  *   - pixel -> unit sphere (spherical_bundle_adjuster.cpp:271-298)
  *       -> sba_keypoints_to_sphere()
  *   - equi2cube::get_all (equi2cube.cpp:12-302)
@@ -872,6 +874,69 @@ int sba_landmarks_register_hampel_device(sba_landmarks* h, const int64_t* idx /*
                                          const void* bearings_dev /* double[3 m], device */, size_t m, const double rot0[3],
                                          const double tran0[3], const sba_landmark_register_hampel_options* opt,
                                          sba_landmark_register_hampel_result* res, void* chi2_out_dev /* double[m], device, or NULL */);
+
+/* ---- the landmark map's descriptors, and a frame associated with the map on the device ------------
+ * The map may keep one f32 descriptor row per landmark, packed, next to its planes.  A map that never receives descriptors
+ * behaves as before, byte for byte, and allocates nothing for them.  On a map that keeps them: sba_landmarks_set / _set_device
+ * drop them (the map is replaced); sba_landmarks_prune with apply moves the kept landmarks' rows to their rank with the planes
+ * (the handle then equals a fresh set + set_descriptors of the kept rows; a dry run moves nothing; pruning to empty keeps dim);
+ * sba_landmarks_append / _append_device add rows that are all NaN, which no frame row is ever associated with until they are
+ * described (the matcher never chooses a train row with a non-finite component); fuse, register*, scores and gather* neither read
+ * nor write them.
+ *
+ * set_descriptors: n_rows must equal the map's n, 1 <= dim <= 256, row_stride_bytes a multiple of 4 and >= 4 dim as for
+ * sba_match_descriptors (a padded cv::Mat passes as is); a second call replaces the rows and may change dim; dim == 0 drops the
+ * descriptors (desc is ignored).  The _device twin takes device rows on the handle's device, 4-byte aligned, complete on return.
+ * descriptor_dim: 0 = the map keeps none.  get_descriptors: rows idx[j] (host indices, any order, repeats allowed, validated in
+ * one pass as for sba_landmarks_gather) or, idx == NULL, all n rows (m is ignored), at a stride of out_stride_bytes.
+ * append_described: sba_landmarks_append plus the new rows' descriptors; allowed when the map keeps descriptors of the same dim
+ * or is empty (it then acts as set plus set_descriptors); the _device twin takes all three arrays on the device, xyz and cov
+ * 16-byte aligned as for sba_landmarks_append_device.                                                                            */
+int sba_landmarks_set_descriptors(sba_landmarks* h, const float* desc, size_t n_rows, int dim, size_t row_stride_bytes);
+int sba_landmarks_set_descriptors_device(sba_landmarks* h, const void* desc_dev, size_t n_rows, int dim, size_t row_stride_bytes);
+int sba_landmarks_descriptor_dim(const sba_landmarks* h, int* dim);
+int sba_landmarks_get_descriptors(sba_landmarks* h, const int64_t* idx /* [m] or NULL: all n rows */, size_t m, float* out,
+                                  size_t out_stride_bytes);
+int sba_landmarks_append_described(sba_landmarks* h, const double* xyz /* double[3 n_add] */, const double* cov /* double[6 n_add] */,
+                                   const float* desc, size_t n_add, int dim, size_t row_stride_bytes, double cov_scale);
+int sba_landmarks_append_described_device(sba_landmarks* h, const void* xyz_dev, const void* cov_dev, const void* desc_dev, size_t n_add,
+                                          int dim, size_t row_stride_bytes, double cov_scale);
+/* sba_landmarks_associate: a frame's descriptors in, idx and the gathered bearings out -- exactly what sba_landmarks_register*_device
+ * takes as idx (host) and bearings_dev.  THE RULE, which the device follows bit for bit:
+ *   1. Match.   sba_match_descriptors' matcher with the frame rows as queries and the map's rows as train rows, unchanged: frame
+ *               row j gets (i0, d0) and (i1, d1) and is ACCEPTED iff i1 >= 0, d0 < ratio * d1 in float and d0 <= max_distance in
+ *               float.
+ *   2. Claim.   Landmark i's claimants are the accepted rows with i0 == i.  Its winner is the claimant smallest in (bits of d0 as
+ *               u32, j), compared lexicographically; d0 >= 0, so the bit order is the value order, and among equal distances the
+ *               lowest frame row wins.
+ *   3. Output.  Output k is the k-th smallest landmark that has a claimant: idx_out[k] = i, row_out[k] its winner, dist_out[k] the
+ *               winner's d0, bearings_out[3 k .. 3 k + 2] a bitwise copy of frame_bearings[3 row .. 3 row + 2] (skipped when either
+ *               pointer is NULL).  idx_out is strictly increasing and row_out has no repeats.
+ *   4. Counts.  n_accepted = n_contested + n_associated; n_frame = m_frame.
+ * Every output holds min(n, m_frame) rows; n_associated of them are written.  n < 2 or m_frame == 0: zeros and SBA_OK (with fewer
+ * than two train rows nothing matches).  A frame row with a non-finite component matches nothing.  ratio: finite and > 0;
+ * max_distance: > 0, +inf for none.  The _device form reads frame_desc_dev (4-byte aligned) and frame_bearings_dev (8-byte
+ * aligned) on the handle's device and writes bearings_out_dev (16-byte aligned) there; idx_out, row_out and dist_out are on the
+ * host in both forms.  The result has the same bytes on every run and for every grid.
+ * Refusals, each before any device call, with nothing written and the handle usable: a NULL handle / opt / res / frame_desc, a
+ * bad option, a dim that is not the map's, a map without descriptors, a bad stride, n or m_frame >= 2^31, a misaligned device
+ * pointer: SBA_ERR_INVALID_ARG; a poisoned handle: SBA_ERR_HIP.                                                                  */
+typedef struct sba_landmark_associate_options {
+  float ratio;        /* the ratio test, as sba_match_descriptors' */
+  float max_distance; /* an accepted row has d0 <= this; +inf: no cut */
+} sba_landmark_associate_options;
+typedef struct sba_landmark_associate_result {
+  long long n_frame, n_accepted, n_contested, n_associated;
+} sba_landmark_associate_result;
+int sba_landmarks_associate(sba_landmarks* h, const float* frame_desc, size_t m_frame, int dim, size_t row_stride_bytes,
+                            const double* frame_bearings /* double[3 m_frame] or NULL */, const sba_landmark_associate_options* opt,
+                            sba_landmark_associate_result* res, int64_t* idx_out, int32_t* row_out, float* dist_out,
+                            double* bearings_out /* each may be NULL */);
+int sba_landmarks_associate_device(sba_landmarks* h, const void* frame_desc_dev, size_t m_frame, int dim, size_t row_stride_bytes,
+                                   const void* frame_bearings_dev /* double[3 m_frame], device, or NULL */,
+                                   const sba_landmark_associate_options* opt, sba_landmark_associate_result* res,
+                                   int64_t* idx_out /* host */, int32_t* row_out /* host */, float* dist_out /* host */,
+                                   void* bearings_out_dev /* double[3 min(n, m_frame)], device, 16-byte aligned, or NULL */);
 
 /* ---- multi-GPU: one process (and one sba_problem) per GPU, correspondences sharded ------ */
 /* Option A: native RCCL.  Rank 0 calls sba_comm_unique_id, ships the 128 bytes to the other

@@ -130,6 +130,14 @@ class LmSummary(C.Structure):
                 ("num_line_search_steps", C.c_int)]
 
 
+class LandmarkAssociateOptions(C.Structure):
+    _fields_ = [("ratio", C.c_float), ("max_distance", C.c_float)]
+
+
+class LandmarkAssociateResult(C.Structure):
+    _fields_ = [("n_frame", C.c_longlong), ("n_accepted", C.c_longlong), ("n_contested", C.c_longlong), ("n_associated", C.c_longlong)]
+
+
 class LandmarkRegisterOptions(C.Structure):
     _fields_ = [("bearing_sigma", C.c_double), ("chi2_gate", C.c_double), ("apply", C.c_int), ("lm", LmOptions)]
 
@@ -270,6 +278,18 @@ SIGNATURES = {
                                                             C.POINTER(LandmarkRegisterHampelOptions), C.POINTER(LandmarkRegisterHampelEval)]),
     "sba_landmarks_register_hampel_device": (C.c_int, [_vp, C.POINTER(C.c_int64), _vp, C.c_size_t, _dp, _dp,
                                                        C.POINTER(LandmarkRegisterHampelOptions), C.POINTER(LandmarkRegisterHampelResult), _vp]),
+    "sba_landmarks_set_descriptors": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_size_t]),
+    "sba_landmarks_set_descriptors_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_size_t]),
+    "sba_landmarks_descriptor_dim": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "sba_landmarks_get_descriptors": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_size_t, _vp, C.c_size_t]),
+    "sba_landmarks_append_described": (C.c_int, [_vp, _dp, _dp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_double]),
+    "sba_landmarks_append_described_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, C.c_int, C.c_size_t, C.c_double]),
+    "sba_landmarks_associate": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_size_t, _dp, C.POINTER(LandmarkAssociateOptions),
+                                          C.POINTER(LandmarkAssociateResult), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_float), _dp]),
+    "sba_landmarks_associate_device": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.c_size_t, _vp, C.POINTER(LandmarkAssociateOptions),
+                                                 C.POINTER(LandmarkAssociateResult), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_float), _vp]),
     "sba_problem_epipolar_moments": (C.c_int, [_vp, _dp]),
     "sba_initial_guess_from_moments": (C.c_int, [_dp, C.c_int, C.c_double, C.c_ulonglong, _dp, _dp,
                                                  C.POINTER(C.c_int)]),

@@ -190,6 +190,22 @@ class LandmarkPrune:
 
 
 @dataclass
+class LandmarkAssociation:
+    """What one Landmarks.associate found.  Frame row j is accepted iff the matcher gives it two neighbours, d0 < ratio * d1 in
+    float32 and d0 <= max_distance in float32; a landmark's winner is its claimant smallest in (bits of d0, j); the outputs list
+    the claimed landmarks in ascending order.  n_accepted = n_contested + n_associated."""
+    n_frame: int
+    n_accepted: int
+    n_contested: int
+    n_associated: int
+    idx: np.ndarray                # (n_associated,) int64, strictly increasing: what register* takes as idx
+    rows: np.ndarray               # (n_associated,) int32: the winning frame row per landmark, no repeats
+    distance: np.ndarray           # (n_associated,) float32: the winner's d0
+    bearings: np.ndarray | None    # (n_associated, 3) float64 = frame_bearings[rows] bit for bit; None without frame bearings or
+    #                                when they went to device memory
+
+
+@dataclass
 class ResectionGuess:
     """The linear starting point of the resection (Problem.resection_guess) and what its moment matrix says about it."""
     rot: np.ndarray        # (3,)
@@ -1360,6 +1376,95 @@ class Landmarks:
         cabi.check(self._lib, self._lib.sba_landmarks_gather_device(self._h, ii.ctypes.data_as(C.POINTER(C.c_int64)), ii.shape[0],
                                                                     C.c_void_p(int(xyz_ptr) if xyz_ptr else 0),
                                                                     C.c_void_p(int(cov_ptr) if cov_ptr else 0)))
+
+    # -- descriptors: a row per landmark, kept in step with the map by set, prune and append ------------
+    def set_descriptors(self, desc) -> None:
+        """One float32 descriptor row (n, dim) per landmark, 1 <= dim <= 256; padded rows (a view of a wider array) pass as they
+        are.  A second call replaces the rows; None or dim 0 drops them."""
+        if desc is None or np.asarray(desc).ndim == 2 and np.asarray(desc).shape[1] == 0:
+            cabi.check(self._lib, self._lib.sba_landmarks_set_descriptors(self._h, None, 0, 0, 0))
+            return
+        (d,), dim, stride = _descriptors(desc)
+        cabi.check(self._lib, self._lib.sba_landmarks_set_descriptors(self._h, C.c_void_p(d.ctypes.data), d.shape[0], dim, stride))
+
+    def set_descriptors_device(self, desc_ptr, n_rows: int, dim: int, row_stride_bytes: int | None = None) -> None:
+        """set_descriptors from DEVICE rows on the handle's device, 4-byte aligned; complete on return."""
+        cabi.check(self._lib, self._lib.sba_landmarks_set_descriptors_device(
+            self._h, C.c_void_p(int(desc_ptr) if desc_ptr else 0), int(n_rows), int(dim), int(4 * dim if row_stride_bytes is None else row_stride_bytes)))
+
+    @property
+    def descriptor_dim(self) -> int:
+        """The dimension of the map's descriptor rows; 0: the map keeps none."""
+        dim = C.c_int(0)
+        cabi.check(self._lib, self._lib.sba_landmarks_descriptor_dim(self._h, C.byref(dim)))
+        return dim.value
+
+    def get_descriptors(self, idx=None) -> np.ndarray:
+        """(n, dim) float32, or rows idx (any order, repeats allowed) as (m, dim)."""
+        dim = self.descriptor_dim
+        ii = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        rows = self.size if ii is None else ii.shape[0]
+        out = np.zeros((rows, dim), dtype=np.float32)
+        cabi.check(self._lib, self._lib.sba_landmarks_get_descriptors(
+            self._h, None if ii is None else ii.ctypes.data_as(C.POINTER(C.c_int64)), rows, C.c_void_p(out.ctypes.data), 4 * max(dim, 1)))
+        return out
+
+    def append_described(self, xyz, cov, desc, cov_scale: float = 1.0) -> None:
+        """append plus the new rows' descriptors (n_add, dim): the map keeps descriptors of this dim, or is empty."""
+        x, c = _f64(xyz).reshape(-1, 3), _f64(cov).reshape(-1, 6)
+        (d,), dim, stride = _descriptors(desc)
+        if x.shape[0] != c.shape[0] or x.shape[0] != d.shape[0]:
+            raise ValueError("one covariance row and one descriptor row per landmark")
+        cabi.check(self._lib, self._lib.sba_landmarks_append_described(self._h, _dptr(x), _dptr(c), C.c_void_p(d.ctypes.data), x.shape[0], dim,
+                                                                       stride, float(cov_scale)))
+
+    def append_described_device(self, xyz_ptr, cov_ptr, desc_ptr, n_add: int, dim: int, cov_scale: float = 1.0,
+                                row_stride_bytes: int | None = None) -> None:
+        """append_described from DEVICE arrays on the handle's device: xyz and cov 16-byte aligned, the descriptors 4-byte."""
+        cabi.check(self._lib, self._lib.sba_landmarks_append_described_device(
+            self._h, C.c_void_p(int(xyz_ptr) if xyz_ptr else 0), C.c_void_p(int(cov_ptr) if cov_ptr else 0),
+            C.c_void_p(int(desc_ptr) if desc_ptr else 0), int(n_add), int(dim), int(4 * dim if row_stride_bytes is None else row_stride_bytes),
+            float(cov_scale)))
+
+    def _associate_out(self, m, ratio, max_distance):
+        cap = min(self.size, int(m))
+        opt = cabi.LandmarkAssociateOptions(float(ratio), float(max_distance))
+        return opt, cabi.LandmarkAssociateResult(), np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.float32)
+
+    @staticmethod
+    def _association(res, idx, rows, dist, bearings) -> LandmarkAssociation:
+        k = int(res.n_associated)
+        return LandmarkAssociation(int(res.n_frame), int(res.n_accepted), int(res.n_contested), k, idx[:k].copy(), rows[:k].copy(),
+                                   dist[:k].copy(), None if bearings is None else bearings[:k].copy())
+
+    def associate(self, frame_desc, frame_bearings=None, ratio: float = 0.3, max_distance: float = float("inf")) -> LandmarkAssociation:
+        """A frame's descriptors (m, dim) against the map's: per claimed landmark its index, the winning frame row, its distance
+        and, with frame_bearings (m, 3), that row's bearing -- what register* takes as idx and bearings (LandmarkAssociation)."""
+        (d,), dim, stride = _descriptors(frame_desc)
+        m = d.shape[0]
+        b = None if frame_bearings is None else _f64(frame_bearings).reshape(-1, 3)
+        if b is not None and b.shape[0] != m:
+            raise ValueError("one bearing per frame row")
+        opt, res, idx, rows, dist = self._associate_out(m, ratio, max_distance)
+        out = None if b is None else np.zeros((idx.shape[0], 3))
+        cabi.check(self._lib, self._lib.sba_landmarks_associate(
+            self._h, C.c_void_p(d.ctypes.data), m, dim, stride, None if b is None else _dptr(b), C.byref(opt), C.byref(res),
+            idx.ctypes.data_as(C.POINTER(C.c_int64)), rows.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_float)),
+            None if out is None else _dptr(out)))
+        return self._association(res, idx, rows, dist, out)
+
+    def associate_device(self, frame_desc_ptr, m: int, dim: int, frame_bearings_ptr=None, bearings_out_ptr=None, ratio: float = 0.3,
+                         max_distance: float = float("inf"), row_stride_bytes: int | None = None) -> LandmarkAssociation:
+        """associate from DEVICE rows on the handle's device (descriptors 4-byte, bearings 8-byte aligned); the gathered bearings
+        go to bearings_out_ptr (device, 16-byte aligned, min(n, m) rows of 3 float64), where register_robust / register_hampel read
+        them in place.  idx, rows and distance come back on the host; `bearings` is None."""
+        opt, res, idx, rows, dist = self._associate_out(m, ratio, max_distance)
+        cabi.check(self._lib, self._lib.sba_landmarks_associate_device(
+            self._h, C.c_void_p(int(frame_desc_ptr) if frame_desc_ptr else 0), int(m), int(dim),
+            int(4 * dim if row_stride_bytes is None else row_stride_bytes), C.c_void_p(int(frame_bearings_ptr) if frame_bearings_ptr else 0),
+            C.byref(opt), C.byref(res), idx.ctypes.data_as(C.POINTER(C.c_int64)), rows.ctypes.data_as(C.POINTER(C.c_int32)),
+            dist.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(int(bearings_out_ptr) if bearings_out_ptr else 0)))
+        return self._association(res, idx, rows, dist, None)
 
 
 class Batch:

@@ -579,6 +579,28 @@ hipError_t launch_landmarks_append(const LandmarkPlanes& src, size_t n_old, cons
 hipError_t launch_landmarks_gather(const LandmarkPlanes& pl, const long long* idx, size_t m, double* xyz, double* cov, unsigned int* counts,
                                    int grid, hipStream_t stream);
 
+// The landmark map's descriptors and the association of a frame (sba_landmarks_associate.hip; the claim key and the checks:
+// sba_landmarks_associate.hpp).  Descriptor rows are packed: row i = dim floats at desc + i * dim.  Desc scatter: the kept rows of
+// src (keep, tile_offset: the very bytes and offsets launch_landmarks_compact_scatter took) to row tile_offset + rank of dst, which
+// must not overlap src.  Desc gather: row j of out = row idx[j] < n.  Claim: matches k < n_matches of the matcher's compacted list
+// (frame row, landmark, distance); one with distance <= max_distance puts its key into slots[landmark] by a 64-bit integer atomic
+// min (slots preset to all ones by the caller) and counts in counters[0] (zeroed by the caller).  Keep: keep[i] = 1 where slot i
+// was claimed, whole tiles, 0 beyond n.  Scatter: block b = tile b; claimed landmark i goes to output tile_offset + rank: idx = i,
+// row and dist = the halves of its key, bearings_out row = a bitwise copy of the winner's row of frame_bearings (both or neither
+// null).  Integer atomics only and no floating-point reduction: the bytes depend neither on the grid nor on the run.
+enum { LANDMARK_ASSOC_CLAIM = 0, LANDMARK_ASSOC_KEEP = 1, LANDMARK_ASSOC_DESC_GATHER = 2, LANDMARK_ASSOC_KERNELS = 3 };
+hipError_t landmarks_associate_blocks_per_cu(int which, int* blocks);   // resident 256-thread blocks per CU of the grid-stride kernels
+hipError_t launch_landmarks_desc_compact_scatter(const unsigned char* keep, size_t n, const unsigned long long* tile_offset, size_t ntiles,
+                                                 const float* src, float* dst, int dim, hipStream_t stream);
+hipError_t launch_landmarks_desc_gather(const float* desc, int dim, const long long* idx, size_t m, float* out, int grid, hipStream_t stream);
+hipError_t launch_landmarks_claim(const int* match_row, const int* match_landmark, const float* match_dist, size_t n_matches, float max_distance,
+                                  unsigned long long* slots, unsigned long long* counters, int grid, hipStream_t stream);
+hipError_t launch_landmarks_associate_keep(const unsigned long long* slots, size_t n, unsigned char* keep, size_t ntiles, int grid,
+                                           hipStream_t stream);
+hipError_t launch_landmarks_associate_scatter(const unsigned char* keep, size_t n, const unsigned long long* tile_offset, size_t ntiles,
+                                              const unsigned long long* slots, const double* frame_bearings, long long* idx_out, int* row_out,
+                                              float* dist_out, double* bearings_out, hipStream_t stream);
+
 // Covariance of the joint solve (sba_covariance.hip; algebra and host finish: sba_covariance.hpp).  prm: a first reduce
 // pass's JointParams with inv_radius = 0.  Reduce: partials [grid][COV_ROW], out (device) the COV_OUT_* slots.  Depth:
 // sigma_c the ambient 6 x 6 camera covariance, out [(n + 1) / 2][6] doubles = (var d1, var d2, cov) per match.

@@ -5,7 +5,9 @@
 // sba_landmarks_edit.hip and their checks in sba_landmarks_edit.hpp, and at the end the joint registration of a frame -- its pose
 // and its landmarks solved together -- with its kernels in sba_landmarks_register.hip and its per-observation code in
 // sba_landmarks_register.hpp, then its robust form (sba_landmarks_register_robust.hpp, sba_landmarks_register_robust.hip) and
-// last that form under Hampel's redescending loss (sba_landmarks_register_hampel.hpp, sba_landmarks_register_hampel.hip).
+// last that form under Hampel's redescending loss (sba_landmarks_register_hampel.hpp, sba_landmarks_register_hampel.hip).  Behind
+// them the map's descriptor rows and the association of a frame with the map (sba_landmarks_associate.hpp,
+// sba_landmarks_associate.hip); the edits above keep those rows in step with the planes.
 // Every wait is the bounded stream_wait; a handle whose wait gave up is poisoned.
 #include <algorithm>
 #include <chrono>
@@ -18,11 +20,13 @@
 
 #include "sba_internal.hpp"
 #include "sba_landmarks.hpp"
+#include "sba_landmarks_associate.hpp"
 #include "sba_landmarks_edit.hpp"
 #include "sba_landmarks_register.hpp"
 #include "sba_landmarks_register_robust.hpp"
 #include "sba_landmarks_register_hampel.hpp"
 #include "sba_lm.hpp"
+#include "sba_match.hpp"
 
 struct sba_landmarks {
   int device = 0;
@@ -53,6 +57,17 @@ struct sba_landmarks {
   int occ_reg[sba::LANDMARK_REGISTER_KERNELS][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};   // per [kernel][indexed][apply]
   int occ_reg_robust[2] = {0, 0};          // ... of landmarks_register_robust_reduce_kernel per [indexed]
   int occ_reg_hampel[2] = {0, 0};          // ... of landmarks_register_hampel_reduce_kernel per [indexed]
+  // The descriptors (at the end of this file): one packed f32 row of desc_dim floats per landmark, desc_dim = 0 while the map keeps
+  // none.  A prune and an append write the other allocation and swap the two, as the planes do.  assoc: the scratch of one
+  // association, kept across calls.  A map that never receives descriptors allocates none of the three.
+  float* desc = nullptr;
+  size_t desc_bytes = 0;
+  float* desc_alt = nullptr;
+  size_t desc_alt_bytes = 0;
+  int desc_dim = 0;
+  void* assoc = nullptr;
+  size_t assoc_bytes = 0;
+  int occ_assoc[sba::LANDMARK_ASSOC_KERNELS] = {0, 0, 0};
 };
 
 namespace {
@@ -181,6 +196,7 @@ int set_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n, dou
   SBA_TRY_HIP(hipSetDevice(h->device));
   const size_t elems = (n + 1) / 2 * 2;
   h->n = 0; h->elems = 0;        // the map is replaced: empty until the new rows are in place
+  h->desc_dim = 0;               // ... and its descriptors go with it
   if (n == 0) return SBA_OK;
   int rc = grow_scratch(&h->planes, &h->planes_bytes, planes_size(elems));
   if (rc) return rc;
@@ -276,6 +292,9 @@ int sba_landmarks_destroy(sba_landmarks* h) {
   if (h->planes_alt) (void)hipFree(h->planes_alt);
   if (h->edit) (void)hipFree(h->edit);
   if (h->reg) (void)hipFree(h->reg);
+  if (h->desc) (void)hipFree(h->desc);
+  if (h->desc_alt) (void)hipFree(h->desc_alt);
+  if (h->assoc) (void)hipFree(h->assoc);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return SBA_OK;
@@ -365,18 +384,66 @@ void swap_planes(sba_landmarks* h, size_t n, size_t elems) {
   h->n = n; h->elems = elems;
 }
 
-int append_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n_add, double cov_scale, bool from_device) {
+// The descriptors through an edit.  The other descriptor allocation, at least `rows` rows of `dim` floats, grown as alt_planes grows.
+int alt_desc(sba_landmarks* h, size_t rows, int dim) {
+  return grow_scratch(&h->desc_alt, &h->desc_alt_bytes, std::max<size_t>(rows, 1) * static_cast<size_t>(dim) * sizeof(float), 2);
+}
+
+// The other descriptor allocation holds the map's rows now.
+void swap_desc(sba_landmarks* h, int dim) {
+  std::swap(h->desc, h->desc_alt);
+  std::swap(h->desc_bytes, h->desc_alt_bytes);
+  h->desc_dim = dim;
+}
+
+// n_rows caller rows of `dim` floats at a stride of stride_bytes into packed rows on the device, on the handle's stream.
+int pack_desc_rows(sba_landmarks* h, float* dst, const void* rows, size_t n_rows, int dim, size_t stride_bytes, bool from_device) {
+  const size_t width = static_cast<size_t>(dim) * sizeof(float);
+  SBA_TRY_HIP(hipMemcpy2DAsync(dst, width, rows, stride_bytes, width, n_rows, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+  return SBA_OK;
+}
+
+// The descriptor rows of an append into the other allocation: the map's own rows, then the caller's n_add rows or, when the
+// caller has none (desc == null), rows that are all NaN -- a train row the matcher never chooses.
+int append_desc_rows(sba_landmarks* h, int dim, const void* desc, size_t n_add, size_t stride_bytes, bool from_device) {
+  const size_t n_old = h->n, row = static_cast<size_t>(dim);
+  int rc = alt_desc(h, n_old + n_add, dim);
+  if (rc) return rc;
+  if (n_old) SBA_TRY_HIP(hipMemcpyAsync(h->desc_alt, h->desc, n_old * row * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  float* added = h->desc_alt + n_old * row;
+  if (desc) return pack_desc_rows(h, added, desc, n_add, dim, stride_bytes, from_device);
+  SBA_TRY_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(added), 0x7fc00000, n_add * row, h->stream));
+  return SBA_OK;
+}
+
+// desc == null: a plain append.  Otherwise n_add descriptor rows of `dim` floats come with the landmarks (sba_landmarks_append_described).
+int append_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n_add, double cov_scale, bool from_device, const void* desc = nullptr,
+                  int dim = 0, size_t row_stride_bytes = 0, bool described = false) {
   if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
   SBA_REFUSE_POISONED(h);
   if (n_add > 0 && (!xyz || !cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark or covariance array");
   if (rows_unaligned(from_device, xyz, cov)) return sba::set_error(SBA_ERR_INVALID_ARG, "the landmark and covariance rows must be 16-byte aligned");
   if (const char* why = sba::resect_weight_check_scale(cov_scale)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s", why);
   if (const char* why = sba::landmark_check_sizes(h->n, n_add)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (n = %zu, n_add = %zu)", why, h->n, n_add);
+  if (described) {
+    if (const char* why = sba::descriptor_check_rows(dim, row_stride_bytes))
+      return sba::set_error(SBA_ERR_INVALID_ARG, "%s (dim = %d, row_stride_bytes = %zu)", why, dim, row_stride_bytes);
+    if (n_add > 0 && !desc) return sba::set_error(SBA_ERR_INVALID_ARG, "null descriptor array");
+    if (from_device && (reinterpret_cast<uintptr_t>(desc) & 3u) != 0) return sba::set_error(SBA_ERR_INVALID_ARG, "device descriptor rows must be 4-byte aligned");
+    if (h->n > 0 && h->desc_dim != dim)
+      return sba::set_error(SBA_ERR_INVALID_ARG, "the map keeps descriptors of dimension %d (0: none), the new rows have %d", h->desc_dim, dim);
+    if (n_add == 0 && h->n == 0) h->desc_dim = dim;      // an empty map takes the dimension, as set + set_descriptors would
+  }
   if (n_add == 0) return SBA_OK;
   SBA_TRY_HIP(hipSetDevice(h->device));
   const size_t n_new = h->n + n_add, elems_new = (n_new + 1) / 2 * 2;
   int rc = alt_planes(h, planes_size(elems_new));
   if (rc) return rc;
+  const int dim_new = described ? dim : h->desc_dim;     // a plain append to a described map: NaN rows
+  if (dim_new) {
+    rc = append_desc_rows(h, dim_new, described ? desc : nullptr, n_add, row_stride_bytes, from_device);
+    if (rc) return rc;
+  }
   const double *xyz_dev = static_cast<const double*>(xyz), *cov_dev = static_cast<const double*>(cov);
   if (!from_device) {
     rc = edit_scratch(h, 9 * n_add * sizeof(double));
@@ -393,6 +460,7 @@ int append_common(sba_landmarks* h, const void* xyz, const void* cov, size_t n_a
   rc = sba::stream_wait(h->stream, "landmark append", &h->poisoned);
   if (rc) return rc;
   swap_planes(h, n_new, elems_new);
+  if (dim_new) swap_desc(h, dim_new);
   return SBA_OK;
 }
 
@@ -512,12 +580,21 @@ int sba_landmarks_prune(sba_landmarks* h, const sba_landmark_prune_options* opt,
     rc = alt_planes(h, planes_size(elems_new));
     if (rc) return rc;
     dst = sba::LandmarkPlanes{h->planes_alt, elems_new};
+    if (h->desc_dim) {
+      rc = alt_desc(h, n_kept, h->desc_dim);
+      if (rc) return rc;
+    }
   }
   SBA_TRY_HIP(sba::launch_landmarks_compact_scatter(keep_dev, n, tile_offset, ntiles, planes_of(h), dst, n_kept, kept ? kept_dev : nullptr, h->stream));
+  if (apply && h->desc_dim)      // the descriptor rows follow the planes: the same keep bytes, the same tile offsets
+    SBA_TRY_HIP(sba::launch_landmarks_desc_compact_scatter(keep_dev, n, tile_offset, ntiles, h->desc, h->desc_alt, h->desc_dim, h->stream));
   if (kept) SBA_TRY_HIP(hipMemcpyAsync(kept, kept_dev, n_kept * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
   rc = sba::stream_wait(h->stream, "landmark compaction", &h->poisoned);
   if (rc) return rc;
-  if (apply) swap_planes(h, n_kept, elems_new);
+  if (apply) {
+    swap_planes(h, n_kept, elems_new);
+    if (h->desc_dim) swap_desc(h, h->desc_dim);
+  }
   return SBA_OK;
 }
 
@@ -1148,6 +1225,248 @@ int sba_landmarks_register_hampel_device(sba_landmarks* h, const int64_t* idx, c
                                          const double tran0[3], const sba_landmark_register_hampel_options* opt, sba_landmark_register_hampel_result* res,
                                          void* chi2_out_dev) {
   return register_hampel_common(h, idx, static_cast<const double*>(bearings_dev), true, m, rot0, tran0, opt, res, static_cast<double*>(chi2_out_dev));
+}
+
+}  // extern "C"
+
+// ---- the descriptors: a row per landmark, and the association of a frame with the map (sba_landmarks_associate.hpp) ----------------
+namespace {
+
+int associate_occ(sba_landmarks* h, int which, int* occ) {
+  return cached_occ(&h->occ_assoc[which], [&](int* o) { return sba::landmarks_associate_blocks_per_cu(which, o); }, occ);
+}
+
+int set_descriptors_common(sba_landmarks* h, const void* desc, size_t n_rows, int dim, size_t row_stride_bytes, bool from_device) {
+  if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
+  SBA_REFUSE_POISONED(h);
+  if (dim == 0) { h->desc_dim = 0; return SBA_OK; }       // the map keeps none from here on; the allocations stay for the next set
+  if (const char* why = sba::descriptor_check_rows(dim, row_stride_bytes))
+    return sba::set_error(SBA_ERR_INVALID_ARG, "%s (dim = %d, row_stride_bytes = %zu)", why, dim, row_stride_bytes);
+  if (n_rows != h->n) return sba::set_error(SBA_ERR_INVALID_ARG, "one descriptor row per landmark: n_rows = %zu, the map holds %zu", n_rows, h->n);
+  if (n_rows > 0 && !desc) return sba::set_error(SBA_ERR_INVALID_ARG, "null descriptor array");
+  if (from_device && (reinterpret_cast<uintptr_t>(desc) & 3u) != 0) return sba::set_error(SBA_ERR_INVALID_ARG, "device descriptor rows must be 4-byte aligned");
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  // into the other allocation, swapped in once the rows are in place: a failed call leaves the old rows
+  int rc = alt_desc(h, n_rows, dim);
+  if (rc) return rc;
+  if (n_rows) {
+    rc = pack_desc_rows(h, h->desc_alt, desc, n_rows, dim, row_stride_bytes, from_device);
+    if (rc) return rc;
+    rc = sba::stream_wait(h->stream, "landmark descriptors", &h->poisoned);
+    if (rc) return rc;
+  }
+  swap_desc(h, dim);
+  return SBA_OK;
+}
+
+// What one association works on, carved from h->assoc; every part starts 256-byte aligned.
+struct AssociateScratch {
+  float* frame = nullptr;                    // packed frame rows [m][dim], when they are not read in place
+  double* bearings = nullptr;                // the frame's bearings [m][3], when they come from the host
+  int *match_row = nullptr, *match_landmark = nullptr;
+  float* match_dist = nullptr;
+  unsigned long long *slots = nullptr, *tile_offset = nullptr, *counters = nullptr;   // counters: accepted, associated
+  unsigned char* keep = nullptr;
+  unsigned int* tile_count = nullptr;
+  long long* idx = nullptr;
+  int* row = nullptr;
+  float* dist = nullptr;
+  double* bearings_out = nullptr;            // [cap][3], when they go to the host
+};
+
+int associate_scratch(sba_landmarks* h, size_t m, int dim, bool stage_frame, bool stage_bearings, bool stage_bearings_out, size_t ntiles,
+                      AssociateScratch* s) {
+  const size_t n = h->n, cap = std::min(n, m);
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { const size_t o = off; off += (std::max<size_t>(bytes, 1) + 255) / 256 * 256; return o; };
+  const size_t o_frame = carve(stage_frame ? m * static_cast<size_t>(dim) * sizeof(float) : 0);
+  const size_t o_bear = carve(stage_bearings ? 3 * m * sizeof(double) : 0);
+  const size_t o_mr = carve(m * sizeof(int)), o_ml = carve(m * sizeof(int)), o_md = carve(m * sizeof(float));
+  const size_t o_slots = carve(n * sizeof(unsigned long long)), o_toff = carve(ntiles * sizeof(unsigned long long));
+  const size_t o_cnt = carve(2 * sizeof(unsigned long long)), o_keep = carve(ntiles * sba::kCompactTile), o_tcount = carve(ntiles * sizeof(unsigned int));
+  const size_t o_idx = carve(cap * sizeof(long long)), o_row = carve(cap * sizeof(int)), o_dist = carve(cap * sizeof(float));
+  const size_t o_bout = carve(stage_bearings_out ? 3 * cap * sizeof(double) : 0);
+  const int rc = grow_scratch(&h->assoc, &h->assoc_bytes, off, 2);
+  if (rc) return rc;
+  char* w = static_cast<char*>(h->assoc);
+  s->frame = reinterpret_cast<float*>(w + o_frame);
+  s->bearings = reinterpret_cast<double*>(w + o_bear);
+  s->match_row = reinterpret_cast<int*>(w + o_mr);
+  s->match_landmark = reinterpret_cast<int*>(w + o_ml);
+  s->match_dist = reinterpret_cast<float*>(w + o_md);
+  s->slots = reinterpret_cast<unsigned long long*>(w + o_slots);
+  s->tile_offset = reinterpret_cast<unsigned long long*>(w + o_toff);
+  s->counters = reinterpret_cast<unsigned long long*>(w + o_cnt);
+  s->keep = reinterpret_cast<unsigned char*>(w + o_keep);
+  s->tile_count = reinterpret_cast<unsigned int*>(w + o_tcount);
+  s->idx = reinterpret_cast<long long*>(w + o_idx);
+  s->row = reinterpret_cast<int*>(w + o_row);
+  s->dist = reinterpret_cast<float*>(w + o_dist);
+  s->bearings_out = reinterpret_cast<double*>(w + o_bout);
+  return SBA_OK;
+}
+
+// Both forms.  on_device: frame_desc, frame_bearings and bearings_out are device pointers; idx_out, row_out and dist_out are on
+// the host in both.  Two waits: the matcher's count, then the associated count with the outputs.  The claim reads the matcher's
+// compacted list of accepted rows, which is on the device when the first wait returns, so no wait stands between them.
+int associate_common(sba_landmarks* h, const void* frame_desc, size_t m, int dim, size_t row_stride_bytes, const void* frame_bearings,
+                     const sba_landmark_associate_options* opt, sba_landmark_associate_result* res, int64_t* idx_out, int32_t* row_out, float* dist_out,
+                     void* bearings_out, bool on_device) {
+  if (!h || !opt || !res || (m > 0 && !frame_desc)) return sba::set_error(SBA_ERR_INVALID_ARG, "null argument");
+  SBA_REFUSE_POISONED(h);
+  if (const char* why = sba::associate_check_options(opt->ratio, opt->max_distance))
+    return sba::set_error(SBA_ERR_INVALID_ARG, "%s (ratio = %g, max_distance = %g)", why, opt->ratio, opt->max_distance);
+  if (h->desc_dim == 0) return sba::set_error(SBA_ERR_INVALID_ARG, "the map keeps no descriptors: sba_landmarks_set_descriptors comes first");
+  if (dim != h->desc_dim) return sba::set_error(SBA_ERR_INVALID_ARG, "the map keeps descriptors of dimension %d, the frame has %d", h->desc_dim, dim);
+  if (const char* why = sba::descriptor_check_rows(dim, row_stride_bytes))
+    return sba::set_error(SBA_ERR_INVALID_ARG, "%s (dim = %d, row_stride_bytes = %zu)", why, dim, row_stride_bytes);
+  if (const char* why = sba::associate_check_sizes(h->n, m)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (n = %zu, m_frame = %zu)", why, h->n, m);
+  if (on_device && ((reinterpret_cast<uintptr_t>(frame_desc) & 3u) != 0 || (reinterpret_cast<uintptr_t>(frame_bearings) & 7u) != 0 ||
+                    (reinterpret_cast<uintptr_t>(bearings_out) & 15u) != 0))
+    return sba::set_error(SBA_ERR_INVALID_ARG, "device rows: descriptors 4-byte, bearings 8-byte, bearings_out 16-byte aligned");
+  *res = sba_landmark_associate_result{};
+  res->n_frame = static_cast<long long>(m);
+  const size_t n = h->n;
+  if (n < 2 || m == 0) return SBA_OK;            // the matcher's rule: with fewer than two train rows nothing matches
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  const bool gather = frame_bearings != nullptr && bearings_out != nullptr;
+  const bool packed = row_stride_bytes == static_cast<size_t>(dim) * sizeof(float);
+  const size_t ntiles = (n + sba::kCompactTile - 1) / sba::kCompactTile;
+  AssociateScratch s;
+  int rc = associate_scratch(h, m, dim, !on_device || !packed, gather && !on_device, gather && !on_device, ntiles, &s);
+  if (rc) return rc;
+  // the frame's rows as the map's are: packed, so that one stride serves both sides of the matcher
+  const float* frame_dev = static_cast<const float*>(frame_desc);
+  if (!on_device || !packed) {
+    rc = pack_desc_rows(h, s.frame, frame_desc, m, dim, row_stride_bytes, on_device);
+    if (rc) return rc;
+    frame_dev = s.frame;
+  }
+  const double* bearings_dev = static_cast<const double*>(frame_bearings);
+  double* bearings_out_dev = static_cast<double*>(bearings_out);
+  if (gather && !on_device) {
+    SBA_TRY_HIP(hipMemcpyAsync(s.bearings, frame_bearings, 3 * m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    bearings_dev = s.bearings;
+    bearings_out_dev = s.bearings_out;
+  }
+  size_t n_matched = 0;
+  rc = sba::match::match_pair_on_stream(h->stream, &h->poisoned, h->num_cus, frame_dev, m, h->desc, n, dim, static_cast<size_t>(dim) * sizeof(float),
+                                        opt->ratio, nullptr, nullptr, &n_matched, s.match_row, s.match_landmark, s.match_dist);   // the first wait
+  if (rc) return rc;
+  if (n_matched == 0) return SBA_OK;
+  if (n_matched > m) return sba::set_error(SBA_ERR_NUMERIC, "the matcher accepted %zu of %zu frame rows", n_matched, m);
+  SBA_TRY_HIP(hipMemsetAsync(s.slots, 0xff, n * sizeof(unsigned long long), h->stream));       // kAssociateUnclaimed
+  SBA_TRY_HIP(hipMemsetAsync(s.counters, 0, 2 * sizeof(unsigned long long), h->stream));
+  int occ = 1;
+  rc = associate_occ(h, sba::LANDMARK_ASSOC_CLAIM, &occ);
+  if (rc) return rc;
+  SBA_TRY_HIP(sba::launch_landmarks_claim(s.match_row, s.match_landmark, s.match_dist, n_matched, opt->max_distance, s.slots, s.counters,
+                                          grid_for(h, n_matched, occ), h->stream));
+  rc = associate_occ(h, sba::LANDMARK_ASSOC_KEEP, &occ);
+  if (rc) return rc;
+  SBA_TRY_HIP(sba::launch_landmarks_associate_keep(s.slots, n, s.keep, ntiles, grid_for(h, ntiles * sba::kCompactTile, occ), h->stream));
+  SBA_TRY_HIP(sba::launch_compact_count(s.keep, ntiles, s.tile_count, h->stream));
+  SBA_TRY_HIP(sba::launch_compact_scan(s.tile_count, ntiles, s.tile_offset, s.counters + 1, h->stream));
+  SBA_TRY_HIP(sba::launch_landmarks_associate_scatter(s.keep, n, s.tile_offset, ntiles, s.slots, gather ? bearings_dev : nullptr, s.idx, s.row, s.dist,
+                                                      gather ? bearings_out_dev : nullptr, h->stream));
+  // No more landmarks are claimed than rows were accepted: that many rows of every output come back with the counts, and the
+  // caller's arrays receive the associated ones after the wait.
+  const size_t fetch = std::min(n_matched, n);
+  unsigned long long host_counts[2] = {0, 0};
+  std::vector<int64_t> idx_host(idx_out ? fetch : 0);
+  std::vector<int32_t> row_host(row_out ? fetch : 0);
+  std::vector<float> dist_host(dist_out ? fetch : 0);
+  std::vector<double> bearings_host(gather && !on_device ? 3 * fetch : 0);
+  SBA_TRY_HIP(hipMemcpyAsync(host_counts, s.counters, sizeof(host_counts), hipMemcpyDeviceToHost, h->stream));
+  if (idx_out) SBA_TRY_HIP(hipMemcpyAsync(idx_host.data(), s.idx, fetch * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  if (row_out) SBA_TRY_HIP(hipMemcpyAsync(row_host.data(), s.row, fetch * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (dist_out) SBA_TRY_HIP(hipMemcpyAsync(dist_host.data(), s.dist, fetch * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (gather && !on_device) SBA_TRY_HIP(hipMemcpyAsync(bearings_host.data(), s.bearings_out, 3 * fetch * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  rc = sba::stream_wait(h->stream, "landmark association", &h->poisoned);                      // the second wait
+  if (rc) return rc;
+  const size_t n_accepted = static_cast<size_t>(host_counts[0]), n_associated = static_cast<size_t>(host_counts[1]);
+  if (n_accepted > n_matched || n_associated > std::min(n_accepted, n))
+    return sba::set_error(SBA_ERR_NUMERIC, "the claim accepted %zu of %zu matched rows and %zu landmarks were claimed", n_accepted, n_matched, n_associated);
+  if (idx_out) std::memcpy(idx_out, idx_host.data(), n_associated * sizeof(int64_t));
+  if (row_out) std::memcpy(row_out, row_host.data(), n_associated * sizeof(int32_t));
+  if (dist_out) std::memcpy(dist_out, dist_host.data(), n_associated * sizeof(float));
+  if (gather && !on_device) std::memcpy(bearings_out, bearings_host.data(), 3 * n_associated * sizeof(double));
+  res->n_accepted = static_cast<long long>(n_accepted);
+  res->n_associated = static_cast<long long>(n_associated);
+  res->n_contested = res->n_accepted - res->n_associated;
+  return SBA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sba_landmarks_set_descriptors(sba_landmarks* h, const float* desc, size_t n_rows, int dim, size_t row_stride_bytes) {
+  return set_descriptors_common(h, desc, n_rows, dim, row_stride_bytes, false);
+}
+
+int sba_landmarks_set_descriptors_device(sba_landmarks* h, const void* desc_dev, size_t n_rows, int dim, size_t row_stride_bytes) {
+  return set_descriptors_common(h, desc_dev, n_rows, dim, row_stride_bytes, true);
+}
+
+int sba_landmarks_descriptor_dim(const sba_landmarks* h, int* dim) {
+  if (!h || !dim) return sba::set_error(SBA_ERR_INVALID_ARG, "null argument");
+  *dim = h->desc_dim;
+  return SBA_OK;
+}
+
+int sba_landmarks_get_descriptors(sba_landmarks* h, const int64_t* idx, size_t m, float* out, size_t out_stride_bytes) {
+  if (!h) return sba::set_error(SBA_ERR_INVALID_ARG, "null landmark handle");
+  SBA_REFUSE_POISONED(h);
+  if (h->desc_dim == 0) return sba::set_error(SBA_ERR_INVALID_ARG, "the map keeps no descriptors");
+  if (const char* why = sba::descriptor_check_rows(h->desc_dim, out_stride_bytes))
+    return sba::set_error(SBA_ERR_INVALID_ARG, "%s (dim = %d, out_stride_bytes = %zu)", why, h->desc_dim, out_stride_bytes);
+  const size_t rows = idx ? m : h->n;
+  if (const char* why = sba::landmark_check_sizes(0, rows)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (m = %zu)", why, rows);
+  if (const char* why = sba::landmark_check_gather_index(idx, idx ? m : 0, h->n)) return sba::set_error(SBA_ERR_INVALID_ARG, "%s (m = %zu, n = %zu)", why, m, h->n);
+  if (rows == 0) return SBA_OK;
+  if (!out) return sba::set_error(SBA_ERR_INVALID_ARG, "null output array");
+  SBA_TRY_HIP(hipSetDevice(h->device));
+  const size_t width = static_cast<size_t>(h->desc_dim) * sizeof(float);
+  const float* rows_dev = h->desc;
+  if (idx) {                     // idx [m] | rows [m][dim] in the edit scratch
+    const size_t o_rows = up16(m * sizeof(int64_t));
+    int rc = edit_scratch(h, o_rows + m * width);
+    if (rc) return rc;
+    long long* idx_dev = static_cast<long long*>(h->edit);
+    float* gathered = reinterpret_cast<float*>(static_cast<char*>(h->edit) + o_rows);
+    SBA_TRY_HIP(hipMemcpyAsync(idx_dev, idx, m * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    int occ = 1;
+    rc = associate_occ(h, sba::LANDMARK_ASSOC_DESC_GATHER, &occ);
+    if (rc) return rc;
+    SBA_TRY_HIP(sba::launch_landmarks_desc_gather(h->desc, h->desc_dim, idx_dev, m, gathered, grid_for(h, m * 16, occ), h->stream));
+    rows_dev = gathered;
+  }
+  SBA_TRY_HIP(hipMemcpy2DAsync(out, out_stride_bytes, rows_dev, width, width, rows, hipMemcpyDeviceToHost, h->stream));
+  return sba::stream_wait(h->stream, "landmark descriptors", &h->poisoned);
+}
+
+int sba_landmarks_append_described(sba_landmarks* h, const double* xyz, const double* cov, const float* desc, size_t n_add, int dim,
+                                   size_t row_stride_bytes, double cov_scale) {
+  return append_common(h, xyz, cov, n_add, cov_scale, false, desc, dim, row_stride_bytes, true);
+}
+
+int sba_landmarks_append_described_device(sba_landmarks* h, const void* xyz_dev, const void* cov_dev, const void* desc_dev, size_t n_add, int dim,
+                                          size_t row_stride_bytes, double cov_scale) {
+  return append_common(h, xyz_dev, cov_dev, n_add, cov_scale, true, desc_dev, dim, row_stride_bytes, true);
+}
+
+int sba_landmarks_associate(sba_landmarks* h, const float* frame_desc, size_t m_frame, int dim, size_t row_stride_bytes, const double* frame_bearings,
+                            const sba_landmark_associate_options* opt, sba_landmark_associate_result* res, int64_t* idx_out, int32_t* row_out,
+                            float* dist_out, double* bearings_out) {
+  return associate_common(h, frame_desc, m_frame, dim, row_stride_bytes, frame_bearings, opt, res, idx_out, row_out, dist_out, bearings_out, false);
+}
+
+int sba_landmarks_associate_device(sba_landmarks* h, const void* frame_desc_dev, size_t m_frame, int dim, size_t row_stride_bytes,
+                                   const void* frame_bearings_dev, const sba_landmark_associate_options* opt, sba_landmark_associate_result* res,
+                                   int64_t* idx_out, int32_t* row_out, float* dist_out, void* bearings_out_dev) {
+  return associate_common(h, frame_desc_dev, m_frame, dim, row_stride_bytes, frame_bearings_dev, opt, res, idx_out, row_out, dist_out,
+                          bearings_out_dev, true);
 }
 
 }  // extern "C"

@@ -270,6 +270,32 @@ int match_host(int device, const float* query, const size_t* qoff, const float* 
 }
 
 }  // namespace
+
+int match_pair_on_stream(hipStream_t stream, int* poisoned, int num_cus, const float* query_dev, size_t n_query, const float* train_dev,
+                         size_t n_train, int dim, size_t row_stride_bytes, float ratio, int* nn_index_dev, float* nn_dist_dev, size_t* n_matched,
+                         int* match_query_dev, int* match_train_dev, float* match_dist_dev) {
+  const size_t qoff[2] = {0, n_query}, toff[2] = {0, n_train};
+  Args a;
+  a.stream = stream;
+  a.poisoned = poisoned;
+  a.num_cus = num_cus;
+  a.query = reinterpret_cast<const uint8_t*>(query_dev);
+  a.train = reinterpret_cast<const uint8_t*>(train_dev);
+  a.qoff = qoff;
+  a.toff = toff;
+  a.num_pairs = 1;
+  a.dim = dim;
+  a.stride = row_stride_bytes;
+  a.ratio = ratio;
+  a.nn_index = nn_index_dev;
+  a.nn_dist = nn_dist_dev;
+  a.match_q = match_query_dev;
+  a.match_t = match_train_dev;
+  a.match_d = match_dist_dev;
+  a.n_matched = n_matched;
+  return run(a);
+}
+
 }  // namespace match
 }  // namespace sba
 
@@ -303,26 +329,12 @@ int sba_match_descriptors_device(int device, void* stream, const float* query_de
     return sba::set_error(SBA_ERR_INVALID_ARG, "null descriptor array");
   rc = sba::match::require_device(device);
   if (rc) return rc;
-  const size_t qoff[2] = {0, n_query}, toff[2] = {0, n_train};
-  sba::match::Args a;
-  rc = sba::match::device_cus(device, &a.num_cus);
+  int num_cus = 0;
+  rc = sba::match::device_cus(device, &num_cus);
   if (rc) return rc;
-  a.stream = static_cast<hipStream_t>(stream);
-  a.query = reinterpret_cast<const uint8_t*>(query_dev);
-  a.train = reinterpret_cast<const uint8_t*>(train_dev);
-  a.qoff = qoff;
-  a.toff = toff;
-  a.num_pairs = 1;
-  a.dim = dim;
-  a.stride = row_stride_bytes;
-  a.ratio = ratio;
-  a.nn_index = nn_index_dev;
-  a.nn_dist = nn_dist_dev;
-  a.match_q = match_query_dev;
-  a.match_t = match_train_dev;
-  a.match_d = match_dist_dev;
-  a.n_matched = n_matched;
-  return sba::match::run(a);
+  return sba::match::match_pair_on_stream(static_cast<hipStream_t>(stream), nullptr, num_cus, query_dev, n_query, train_dev, n_train, dim,
+                                          row_stride_bytes, ratio, nn_index_dev, nn_dist_dev, n_matched, match_query_dev, match_train_dev,
+                                          match_dist_dev);
 }
 
 int sba_batch_match_descriptors(int device, const float* query, const size_t* query_offsets, const float* train,

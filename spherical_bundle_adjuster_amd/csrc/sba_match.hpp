@@ -56,6 +56,14 @@ hipError_t launch_match_scatter(const unsigned char* keep, size_t total_rows, si
                                 int* match_t, float* match_d, unsigned long long* rows_q, unsigned long long* rows_t,
                                 hipStream_t stream);
 
+namespace match {
+// The code behind sba_match_descriptors_device, for a caller with a stream and a handle of its own (sba_match.cpp): one pair of
+// device arrays, the checks done by the caller; a wait that gives up sets *poisoned (may be null).  One synchronisation: the count.
+int match_pair_on_stream(hipStream_t stream, int* poisoned, int num_cus, const float* query_dev, size_t n_query, const float* train_dev,
+                         size_t n_train, int dim, size_t row_stride_bytes, float ratio, int* nn_index_dev, float* nn_dist_dev, size_t* n_matched,
+                         int* match_query_dev, int* match_train_dev, float* match_dist_dev);
+}  // namespace match
+
 // sba_side.hip: the pixel -> unit sphere maps of key-point records picked by absolute row (rows[i] * stride_bytes).
 hipError_t launch_keypoints_to_planes_gather(const uint8_t* kp_left, const uint8_t* kp_right, const unsigned long long* rows_left,
                                              const unsigned long long* rows_right, size_t n, size_t stride_bytes, double im_w,
